@@ -12,13 +12,18 @@ i.e. main.c:197-274.  The solve runs in native mode by default: the
 reference's own mgVRecursive does not converge on this grid (DESIGN.md
 section 6; --mg reference runs it anyway).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Rank 0 prints one JSON line.  value = particles x K / (max over ranks of the
 K-step wall time).  Every probed kernel's launches inside the timed region
 are timed with HIP events on the library's stream; `roofline` reports the
 one with the most time per step, `kernels` all of them.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes the state the last timed step left (see
+_dump_outputs).  --full adds the legs that take runs of their own: the CPU
+baseline (`cpu_baseline`, the oracle on the host cores).
 """
 from __future__ import annotations
 
@@ -257,6 +262,39 @@ def _multi_rank_summary(info: list, steps: int, dom: str, transport: str) -> dic
     return out
 
 
+DUMP_POINTS = 1 << 20   # grid points per dumped field: 48 MiB in all at the largest
+DUMP_SEED = 20260101
+
+
+def _dump_outputs(sim, out_dir: Path, rank: int) -> None:
+    """What the timed steps left with their caller, as <name>.npy (float64)
+    under out_dir: rho, phi and E at the interior grid points (ghost layers
+    dropped), the energies [KE, PE, KE of each species] and each species'
+    particle count.  rho is the deposit of every particle's position, the
+    energies sum every particle's velocity; the particle arrays themselves
+    are not dumped (their order is the tile sort's, and at C4 they are
+    ~100 GB).  A grid of more than DUMP_POINTS points is sampled at a fixed,
+    seeded set of points, the same for all three fields, listed in
+    grid_points.npy (flat indices into the interior grid, z slowest).  Ranks
+    above 0 write <name>.rank<r>.npy of their own slab."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    sfx = f".rank{rank}" if rank else ""
+    nd = sim.ndims
+    inner = (slice(1, -1),) * nd
+    fields = {name: sim.grid(which)[inner] for which, name in enumerate(("rho", "phi", "E"))}
+    npts = int(np.prod(fields["rho"].shape[:nd]))
+    pick = None
+    if npts > DUMP_POINTS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(npts, DUMP_POINTS, replace=False))
+        np.save(out_dir / f"grid_points{sfx}.npy", pick.astype(np.float64))
+    for name, g in fields.items():
+        g = g.reshape(npts, -1)
+        np.save(out_dir / f"{name}{sfx}.npy", np.ascontiguousarray(g if pick is None else g[pick], dtype=np.float64))
+    ke, pe, kes = sim.energy()
+    np.save(out_dir / f"energy{sfx}.npy", np.array([ke, pe, *kes], dtype=np.float64))
+    np.save(out_dir / f"counts{sfx}.npy", np.array([sim.count(s) for s in range(sim.nspecies)], dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -321,7 +359,13 @@ def main() -> int:
                          "to this multiple of its size right after the last sort (0: off)")
     ap.add_argument("--sort-in-push", type=int, default=1,
                     help="1: the tile sort rides in every sort-interval-th push (default); 0: separate sort pass")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (rho, phi, E, energies, particle counts) "
+                         "as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the oracle on the host "
+                         "cores, one GPU only; cpu_baseline in the result line, null without --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-size", type=int, default=None,
                     help="CPU baseline grid (default: the GPU line's, if the host has the memory, else 128)")
     ap.add_argument("--cpu-steps", type=int, default=None, help="CPU baseline steps (default 3 at 256^3, 20 below)")
@@ -651,10 +695,12 @@ def main() -> int:
         result["roofline"]["traffic"] = tr["bytes_per_launch"]
         result["roofline"]["traffic_source"] = tr["source"]
         result["roofline"]["traffic_ratio"] = tr["bytes_per_launch"] / dk["bytes_per_launch"]
+    if args.dump_outputs:
+        _dump_outputs(sim, Path(args.dump_outputs), rank)
     sim.close()
     os.unlink(ini)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_size, note = args.cpu_size, ""
         if cpu_size is None:
             # the full grid when the host holds the oracle's particles (AoS

@@ -8,7 +8,7 @@ export TMPDIR=/tmp PINC_QUIET=1
 T=${1:-final}
 O=gpurun_out/$T
 mkdir -p $O
-timeout -k 10 600 python -u bench.py > $O/bench_c4.json 2> $O/bench_c4.err || { tail -20 $O/bench_c4.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench_c4.json 2> $O/bench_c4.err || { tail -20 $O/bench_c4.err; exit 1; }
 cat $O/bench_c4.json
 bash tools/profile_bench.sh --steps 10 --warmup 3 > $O/profile.log 2>&1 || { tail -20 $O/profile.log; exit 1; }
 python3 tools/kernel_gaps.py gpurun_out/prof 12 > $O/${T}_kernel_gaps.txt || exit 1
