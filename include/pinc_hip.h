@@ -112,7 +112,12 @@ int pinc_hip_move_classify(pinc_pop_t pop, int s, int doMove, const double *thr,
  * puMove's drift, the classification of pinc_hip_move_classify (flags,
  * chunkCount -- zeroed by the caller -- errFlag, wrapMask) and the CIC
  * deposit (puDistr3D1/ND1 weights) of every particle that stays into the
- * species accumulator rhoS (slab layout, not zeroed here).
+ * species accumulator rhoS (slab layout, not zeroed here).  With the slab
+ * dimension wrapped in place (wrapMask bit nd-1) a block that straddles that
+ * boundary deposits at the periodic images of its cells, so a node's charge
+ * may lie on ghost plane 0 or on true plane nloc (nloc+1 or 1): only the sum
+ * after the halo fold (pinc_hip_fold_self) is defined, and E's ghost planes
+ * must be the periodic copies (plane 0 = plane nloc, plane nloc+1 = plane 1).
  *   cursor == NULL: particle i stays at i; new positions go to xout (may be
  *     pop.x), velocities to vout (may be pop.v).
  *   cursor != NULL (tiled layout, sorted output): particle i goes to slot
@@ -120,6 +125,9 @@ int pinc_hip_move_classify(pinc_pop_t pop, int s, int doMove, const double *thr,
  *     current positions, pinc_hip_count_keys + pinc_hip_scan_keys), its
  *     moved state to xout/vout at that slot (must not alias pop), flags at
  *     that slot; chunkCount counts emigrants per destination chunk.
+ *     key(x_i) is the key pinc_hip_count_keys counts: that of the brick
+ *     holding the cell of x_i + v_i, both as the push reads them (before
+ *     its kick and drift), clamped to the grid.
  *     Otherwise (cursor == NULL) the keys of the moved particles that stay
  *     are counted into cntNext if set (zeroed by the caller); a sorting
  *     push does not count. */

@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from push_abi import Geom, Pop
+
 pytestmark = pytest.mark.gpu
 
 
@@ -94,16 +96,6 @@ def test_double_sweep_equals_two_sweeps(hip, shape):
 def test_fused_sweep_rejects_untiled_level(hip):
     L = Lvl(3, (C.c_int * 3)(24, 16, 16))
     assert hip.pinc_hip_gs_sweep(None, None, None, L, None) != 0
-
-
-class Geom(C.Structure):
-    _fields_ = [("nd", C.c_int), ("T", C.c_int * 3), ("nloc", C.c_int), ("off", C.c_int), ("nranks", C.c_int),
-                ("literal", C.c_int)]
-
-
-class Pop(C.Structure):
-    _fields_ = [("x", C.c_void_p * 3), ("v", C.c_void_p * 3), ("nSpecies", C.c_int), ("nd", C.c_int),
-                ("iStart", C.c_long * 9), ("iStop", C.c_long * 8)]
 
 
 @pytest.mark.parametrize("n,T,start", [(100_000, (16, 16, 16), 0), (77_777, (32, 16, 8), 13), (5, (8, 8, 8), 1)])

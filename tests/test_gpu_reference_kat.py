@@ -32,19 +32,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from push_abi import Geom, Pop, PushArgs, device_pop as _device_pop
+
 pytestmark = pytest.mark.gpu
 
 GOLD = json.loads((Path(__file__).parent / "golden" / "reference_outputs.json").read_text())["kat"]
-
-
-class Geom(C.Structure):
-    _fields_ = [("nd", C.c_int), ("T", C.c_int * 3), ("nloc", C.c_int), ("off", C.c_int), ("nranks", C.c_int),
-                ("literal", C.c_int)]
-
-
-class Pop(C.Structure):
-    _fields_ = [("x", C.c_void_p * 3), ("v", C.c_void_p * 3), ("nSpecies", C.c_int), ("nd", C.c_int),
-                ("iStart", C.c_long * 9), ("iStop", C.c_long * 8)]
 
 
 @pytest.fixture(scope="module")
@@ -58,24 +50,6 @@ def hip(built):
     h.pinc_hip_deposit.argtypes = [Pop, C.c_int, Geom, vp, vp]
     h.pinc_hip_move_classify.argtypes = [Pop, C.c_int, C.c_int, vp, vp, vp, C.c_double, vp, C.c_int, vp]
     return h
-
-
-def _device_pop(pos: np.ndarray, vel: np.ndarray, start: int = 0):
-    """Species 0 at [start, start + n) of SoA device arrays (torch memory)."""
-    import torch
-    n = pos.shape[0]
-    cap = start + n + 5
-    xs, vs = [], []
-    for d in range(3):
-        a = np.zeros(cap)
-        a[start:start + n] = pos[:, d]
-        b = np.zeros(cap)
-        b[start:start + n] = vel[:, d]
-        xs.append(torch.from_numpy(a).cuda())
-        vs.append(torch.from_numpy(b).cuda())
-    pop = Pop((C.c_void_p * 3)(*[t.data_ptr() for t in xs]), (C.c_void_p * 3)(*[t.data_ptr() for t in vs]), 1, 3,
-              (C.c_long * 9)(start, cap), (C.c_long * 8)(start + n))
-    return pop, xs, vs
 
 
 def _geom(T):
@@ -179,18 +153,6 @@ def test_const_e_leapfrog_known_answer(hip, qm):
         assert abs(x - (x0 + 0.5 * qm * step * step)) < k["tol"], (qm, step, x)
         assert float(xs[1][0]) == 17.0 and float(xs[2][0]) == 17.0
     assert int(flags[0]) == 13 and int(cnt[0]) == 0 and int(err[0]) == 0   # stays in the subdomain
-
-
-class PushArgs(C.Structure):
-    """pinc_push_t (include/pinc_hip.h)."""
-    _fields_ = [("xout", C.c_void_p * 3), ("vout", C.c_void_p * 3), ("kick", C.c_int), ("Es", C.c_void_p),
-                ("rhoS", C.c_void_p), ("thr", C.c_void_p), ("flags", C.c_void_p), ("chunkCount", C.c_void_p),
-                ("maxVel", C.c_double), ("errFlag", C.c_void_p), ("wrapMask", C.c_int), ("kePartial", C.c_void_p),
-                ("tileWidth", C.c_int), ("cursor", C.c_void_p), ("cntNext", C.c_void_p), ("moved", C.c_void_p),
-                ("spread", C.c_void_p), ("tstamp", C.c_void_p), ("diag", C.c_void_p), ("objInside", C.c_void_p),
-                ("objSy", C.c_long), ("objSz", C.c_long), ("objNodes", C.c_long), ("objCount", C.c_void_p),
-                ("objLo", C.c_int * 3), ("objHi", C.c_int * 3), ("emigTotal", C.c_void_p),
-                ("flagsSparse", C.c_int)]
 
 
 def _embedded_fractions(rho_dev: np.ndarray, T, k):
