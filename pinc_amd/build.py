@@ -19,13 +19,18 @@ ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "pinc_amd" / "csrc"
 HOST = ROOT / "pinc_amd" / "host"
 # PINC_LIBDIR / PINC_HIP_DEFINES: a variant build (kernel experiments) next to
-# the default one, e.g. PINC_LIBDIR=pinc_amd/lib_i2 PINC_HIP_DEFINES="-DPINC_PUSH_ITEMS=2"
+# the default one, e.g. PINC_LIBDIR=pinc_amd/lib_x PINC_HIP_DEFINES="-DMY_EXPERIMENT=2"
+# (the experiment's own temporary macro; the kernels carry no standing switches)
 LIB = Path(os.environ.get("PINC_LIBDIR") or ROOT / "pinc_amd" / "lib").resolve()
 OBJ = ROOT / "build" / ("obj" if LIB == (ROOT / "pinc_amd" / "lib").resolve() else "obj_" + LIB.name)
 INC = ROOT / "include"
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-ARCH = os.environ.get("PINC_ARCH", "gfx950")
+# The kernels use gfx950-only instructions (v_permlane16_swap,
+# v_permlane32_swap) unconditionally.
+ARCH = os.environ.get("PINC_ARCH") or "gfx950"
+if ARCH != "gfx950":
+    sys.exit(f"pinc_amd.build: PINC_ARCH={ARCH} is not supported, the kernels build for gfx950 only")
 # -ffp-contract=off: the kernels reproduce the reference's fp64 association
 # order; a fused multiply-add would change the rounding.
 # build_flags.txt records what a library was built with (arch, compiler,

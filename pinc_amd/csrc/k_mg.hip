@@ -28,16 +28,6 @@ constexpr int kMaxBlocks = 2048;
 
 inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
-
-// 1: the 3-D residual norm on x pairs (k_residual_sumsq3p)
-#ifndef PINC_MG_NORM_PAIRS
-#define PINC_MG_NORM_PAIRS 1
-#endif
-// 1: the level-0 residual and restriction on x pairs (k_resid_restrict3p)
-#ifndef PINC_MG_RR_PAIRS
-#define PINC_MG_RR_PAIRS 1
-#endif
-
 struct Lv {
 	int T[3];
 	long s[3];
@@ -337,33 +327,9 @@ constexpr int kSwH = kSwT + 4; // with the two-node halo
 constexpr int kSwR = kSwT + 2; // red region: tile plus one
 constexpr int kSwZ = 16;       // planes per workgroup
 
-
-// XCD-aware tile order for the z-marching sweeps (PINC_MG_XCD): blocks are
-// dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md, workgroup
-// dispatch), so block b runs on XCD b % 8.  Map it to tile
-// x*q + min(x, r) + y (x = b % 8, y = b / 8) so that each XCD sweeps a
-// contiguous run of tiles, whose x and y halo reads are its neighbours'
-// interiors in the same L2.  A bijection for any grid, placement only.
-// Measured neutral at C4 (k_gs_sweep4 0.192 ms either way: the march is
-// latency-bound, not L2-miss bound), so off by default.
-#ifndef PINC_MG_S4_SPLIT
-#define PINC_MG_S4_SPLIT 1
-#endif
-#ifndef PINC_MG_SWEEP4C
-#define PINC_MG_SWEEP4C 1
-#endif
-#ifndef PINC_MG_XCD
-#define PINC_MG_XCD 0
-#endif
-__device__ __forceinline__ unsigned xcd_tile(unsigned b, unsigned nb) {
-#if PINC_MG_XCD
-	const unsigned x = b & 7u, y = b >> 3, q = nb >> 3, r = nb & 7u;
-	return x * q + min(x, r) + y;
-#else
-	(void)nb;
-	return b;
-#endif
-}
+// Blocks take the tiles in launch order.  An XCD-aware tile order (each XCD a
+// contiguous run of tiles) measured neutral at C4 (the two-iteration sweep
+// 0.192 ms either way: the march is latency-bound, not L2-miss bound).
 
 __global__ __launch_bounds__(256) void k_gs_sweep(const double *__restrict__ phiIn,
                                                   double *__restrict__ phiOut,
@@ -375,7 +341,7 @@ __global__ __launch_bounds__(256) void k_gs_sweep(const double *__restrict__ phi
 	const int TX = Lp.T[0], TY = Lp.T[1], TZ = Lp.T[2];
 	const long sy = TX, sz = (long)TX * TY;
 	const int ntx = TX / kSwT, nty = TY / kSwT;
-	const unsigned tb = xcd_tile(blockIdx.x, gridDim.x);
+	const unsigned tb = blockIdx.x;
 	const int bx = tb % ntx, by = (tb / ntx) % nty, bz = tb / (ntx * nty);
 	const int x0 = bx * kSwT, y0 = by * kSwT, z0 = bz * kSwZ;
 	const int tid = threadIdx.x;
@@ -494,7 +460,7 @@ __global__ __launch_bounds__(kS2Threads) void k_gs_sweep2(const double *__restri
 	const int TX = Lp.T[0], TY = Lp.T[1], TZ = Lp.T[2];
 	const long sy = TX, sz = (long)TX * TY;
 	const int ntx = TX / kS2X, nty = TY / kS2Y;
-	const unsigned tb = xcd_tile(blockIdx.x, gridDim.x);
+	const unsigned tb = blockIdx.x;
 	const int bx = tb % ntx, by = (tb / ntx) % nty, bz = tb / (ntx * nty);
 	const int x0 = bx * kS2X, y0 = by * kS2Y, z0 = bz * zPlanes;
 	const int tid = threadIdx.x;
@@ -605,176 +571,21 @@ __global__ __launch_bounds__(kS2Threads) void k_gs_sweep2(const double *__restri
 // it left it (in place: a stage overwrites only values no later stage
 // needs), so a step costs two barriers.  Each stage is computed on a region
 // one node wider than the next, so the tile needs a four-node halo and no
-// exchange with its neighbours.  rho is not staged: every thread loads the
-// rho values of its own stage nodes two steps ahead into registers, which
-// keeps the LDS at 40 KB and four workgroups on a CU (the march is
-// latency-bound: a step waits for loads issued two steps earlier).  phiIn is read and phiOut
-// written once per two iterations; the arithmetic is that of mgGS3D's red
-// and black passes, so the result is bit-identical to two k_gs_sweep2
-// launches.
-template <int SX, int SY, int NT>
-struct Sweep4 {
-	static constexpr int H = 4;  // phi halo
-	static constexpr int HX = SX + 2 * H, HY = SY + 2 * H;
-	static constexpr int NP = 8;  // ring planes
-	static constexpr int PhiSlots = (HX * HY + NT - 1) / NT;
-	// nodes of one colour on the tile grown by h (rows have even length)
-	static constexpr int nodes(int h) { return (SX + 2 * h) / 2 * (SY + 2 * h); }
-	static constexpr int K3 = (nodes(3) + NT - 1) / NT, K2 = (nodes(2) + NT - 1) / NT,
-	                     K1 = (nodes(1) + NT - 1) / NT;
-};
-
-template <int SX, int SY, int NT>
-__global__ __launch_bounds__(NT) void k_gs_sweep4(const double *__restrict__ phiIn, double *__restrict__ phiOut,
-                                                  const double *__restrict__ rho, pinc_lvl_t Lp, int zPlanes) {
-	using S = Sweep4<SX, SY, NT>;
-	constexpr int HX = S::HX, HY = S::HY, H = S::H, K3 = S::K3, K2 = S::K2, K1 = S::K1;
-	__shared__ double cur[S::NP][HY][HX];
-	const int TX = Lp.T[0], TY = Lp.T[1], TZ = Lp.T[2];
-	const long sy = TX, sz = (long)TX * TY;
-	const int ntx = TX / SX, nty = TY / SY;
-	const unsigned tb = xcd_tile(blockIdx.x, gridDim.x);
-	const int bx = tb % ntx, by = (tb / ntx) % nty, bz = tb / (ntx * nty);
-	const int x0 = bx * SX, y0 = by * SY, z0 = bz * zPlanes;
-	const int tid = threadIdx.x;
-	auto wrapi = [](int i, int T) { return i < 0 ? i + T : (i >= T ? i - T : i); };
-	auto gidx = [&](int x, int y, int z) {
-		return (long)wrapi(x, TX) + wrapi(y, TY) * sy + (long)wrapi(z, TZ) * sz;
-	};
-	auto ps = [](int z) { return (z + 8 * 16) % S::NP; };
-	auto fetch = [&](int zf, double *f) {
-#pragma unroll
-		for (int k = 0; k < S::PhiSlots; k++) {
-			int i = tid + NT * k;
-			if (i < HX * HY) f[k] = phiIn[gidx(x0 + i % HX - H, y0 + i / HX - H, zf)];
-		}
-	};
-	auto putPhi = [&](int zf, const double *f) {
-#pragma unroll
-		for (int k = 0; k < S::PhiSlots; k++) {
-			int i = tid + NT * k;
-			if (i < HX * HY) cur[ps(zf)][i / HX][i % HX] = f[k];
-		}
-	};
-	// node j of colour `parity` on plane p, tile grown by h: tile coordinates
-	auto node = [&](int j, int p, int parity, int h, int &tx, int &ty) {
-		const int hw = (SX + 2 * h) / 2;
-		ty = j / hw - h;
-		tx = -h + 2 * (j % hw) + ((parity - (x0 - h + y0 + ty + p)) & 1);
-	};
-	// rho of this thread's nodes in the four stages of step s
-	struct Rho {
-		double r1[K3], b1[K2], r2[K1], b2;
-	};
-	auto fetchRho = [&](int s, Rho &R) {
-		int tx, ty;
-#pragma unroll
-		for (int k = 0; k < K3; k++) {
-			const int j = tid + NT * k;
-			if (j < S::nodes(3)) {
-				node(j, s + 3, 0, 3, tx, ty);
-				R.r1[k] = rho[gidx(x0 + tx, y0 + ty, s + 3)];
-			}
-		}
-#pragma unroll
-		for (int k = 0; k < K2; k++) {
-			const int j = tid + NT * k;
-			if (j < S::nodes(2)) {
-				node(j, s + 2, 1, 2, tx, ty);
-				R.b1[k] = rho[gidx(x0 + tx, y0 + ty, s + 2)];
-			}
-		}
-#pragma unroll
-		for (int k = 0; k < K1; k++) {
-			const int j = tid + NT * k;
-			if (j < S::nodes(1)) {
-				node(j, s, 0, 1, tx, ty);
-				R.r2[k] = rho[gidx(x0 + tx, y0 + ty, s)];
-			}
-		}
-		R.b2 = rho[gidx(x0 + tid % SX, y0 + tid / SX, s - 2)];
-	};
-	// colour `parity` of plane p on the tile grown by h, in place
-	auto stage = [&](int p, int parity, int h, const double *rv, int nk) {
-		double(*c)[HX] = cur[ps(p)];
-		double(*cm)[HX] = cur[ps(p - 1)];
-		double(*cp)[HX] = cur[ps(p + 1)];
-#pragma unroll
-		for (int k = 0; k < 2; k++) {
-			const int j = tid + NT * k;
-			if (k >= nk || j >= S::nodes(h)) break;
-			int tx, ty;
-			node(j, p, parity, h, tx, ty);
-			const int cx = tx + H, cy = ty + H;
-			double xp = c[cy][cx + 1], xm = c[cy][cx - 1];
-			double yp = c[cy + 1][cx], ym = c[cy - 1][cx];
-			double zp = cp[cy][cx], zm = cm[cy][cx];
-			c[cy][cx] = (1. / 6.) * (xp + xm + yp + ym + zp + zm + rv[k]);
-		}
-	};
-	static_assert(K3 <= 2 && K2 <= 2 && K1 <= 2, "stage loops are unrolled twice");
-	static_assert(SX * SY == NT, "one output node per thread and plane");
-
-	// prologue: phi z0-4 .. z0-2 into LDS, z0-1 into registers A; rho of
-	// the first two steps
-	double fa[S::PhiSlots], fb[S::PhiSlots];
-	for (int z = z0 - 4; z <= z0 - 2; z++) {
-		fetch(z, fb);
-		putPhi(z, fb);
-	}
-	fetch(z0 - 1, fa);
-	Rho RA, RB, RC;
-	fetchRho(z0 - 6, RA);
-	fetchRho(z0 - 5, RB);
-	__syncthreads();
-	const int tx = tid % SX, ty = tid / SX;
-	const int zEnd = z0 + zPlanes;  // outputs z0 .. zEnd-1
-	for (int s = z0 - 6; s <= zEnd + 1; s++) {
-		// LDS: phi s-3 .. s+4 (those each stage reads)
-		if (s <= zEnd) {  // two steps ahead of their use
-			fetch(s + 6, fb);
-			fetchRho(s + 2, RC);
-		}
-		if (s + 3 <= zEnd + 2) stage(s + 3, 0, 3, RA.r1, K3);          // red, 1st iteration
-		if (s >= z0 - 1 && s <= zEnd) stage(s, 0, 1, RA.r2, K1);       // red, 2nd
-		if (s - 2 >= z0 && s - 2 < zEnd) {                              // black, 2nd: out
-			const int zo = s - 2;
-			double(*c)[HX] = cur[ps(zo)];
-			double(*cm)[HX] = cur[ps(zo - 1)];
-			double(*cp)[HX] = cur[ps(zo + 1)];
-			const int gx = x0 + tx, gy = y0 + ty, cx = tx + H, cy = ty + H;
-			double v = c[cy][cx];
-			if (((gx + gy + zo) & 1) != 0) {
-				double xp = c[cy][cx + 1], xm = c[cy][cx - 1];
-				double yp = c[cy + 1][cx], ym = c[cy - 1][cx];
-				double zp = cp[cy][cx], zm = cm[cy][cx];
-				v = (1. / 6.) * (xp + xm + yp + ym + zp + zm + RA.b2);
-			}
-			phiOut[gidx(gx, gy, zo)] = v;
-		}
-		__syncthreads();
-		if (s + 2 >= z0 - 2 && s + 2 <= zEnd + 1) stage(s + 2, 1, 2, RA.b1, K2);  // black, 1st
-		// phi s+5 into the slot of s-3 (last read by the black output above)
-		putPhi(s + 5, fa);
-		__syncthreads();
-#pragma unroll
-		for (int k = 0; k < S::PhiSlots; k++) fa[k] = fb[k];
-		RA = RB;
-		RB = RC;
-	}
-}
-
-// k_gs_sweep4 restructured for instruction count (same stages, ring and
-// arithmetic, bit-identical results).  The profile of k_gs_sweep4 at 256^3
-// (profiles/r02s_mg_pmc*.json) is issue-bound, not HBM-bound: per wave 8.7 k
+// exchange with its neighbours.  phiIn is read and phiOut written once per
+// two iterations; the arithmetic is that of mgGS3D's red and black passes, so
+// the result is bit-identical to two k_gs_sweep2 launches.
+//
+// Written for instruction count.  The profile of a plain version (a
+// [plane][y][x] ring, indices computed per update) at 256^3
+// (profiles/r02s_mg_pmc*.json) was issue-bound, not HBM-bound: per wave 8.7 k
 // VALU and 17 k SALU instructions for 72 plane steps, and LDS bank
 // conflicts on the checkerboard (lanes two doubles apart).  Here
 //   * the LDS ring stores each row split by x parity ([y][x & 1][x >> 1]),
 //     so a stage's nodes -- one colour, hence one x parity per row -- and
 //     their y and z neighbours are consecutive doubles across lanes, and
 //     the two x neighbours are a consecutive pair (one ds_read2);
-//   * every per-node LDS index and global rho offset is computed once per
-//     thread and plane parity, before the march;
+//   * every per-node LDS index is computed once per thread and plane
+//     parity, before the march;
 //   * the march is unrolled over the 8 ring planes, so plane slots, plane
 //     parities and the phi double buffer are compile-time, and LDS
 //     addresses are a per-thread base plus an immediate offset;
@@ -784,44 +595,27 @@ struct Sweep4c {
 	static constexpr int H = 4;
 	static constexpr int HX = SX + 2 * H, HY = SY + 2 * H, HW = HX / 2;
 	static constexpr int PL = HX * HY;  // doubles per ring plane
-	static constexpr int PhiSlots = (PL + NT - 1) / NT;
 	static constexpr int nodes(int h) { return (SX + 2 * h) / 2 * (SY + 2 * h); }
 	static_assert(nodes(3) <= 2 * NT && nodes(2) <= NT && nodes(1) <= NT, "stage slots");
 	static_assert(SX * SY == NT, "one output node per thread and plane");
-	static_assert(PhiSlots == 3, "phi fetch slots");
 };
 
 struct S4Node {
 	unsigned li, lxm;  // LDS indices of the node and of its x-1 neighbour (x+1 follows)
-	unsigned roff;     // byte offset of the node in a plane of the level
+	unsigned roff;     // byte offset of the node in a plane of the level (unused, see k_gs_sweep4c)
 };
 
-// diagnostics only (timing by elimination, wrong results): bit 0 skips the
-// rho loads, bit 1 the phi fetch, bit 2 pads LDS to two workgroups per CU
-#ifndef PINC_MG_S4_DIAG
-#define PINC_MG_S4_DIAG 0
-#endif
-// 1: rho rides in an LDS ring of its own, fetched like phi (three
-// row-contiguous loads per thread and step) and read by each stage from its
-// node's LDS index; 0: each thread gathers the rho of its four stages' nodes
-// from memory (five colour-strided 8-B gathers per step, every value loaded
-// four times).  Elimination builds (PINC_MG_S4_DIAG) put the gathers at half
-// the launch: 0.168 ms with them, 0.089 ms without, while halving the
-// workgroups per CU costs 5 %; the ring takes 80 KB, two workgroups per CU
-#ifndef PINC_MG_S4_RHOLDS
-#define PINC_MG_S4_RHOLDS 1
-#endif
-// with the rho ring: phi and rho planes fetched this many steps ahead of
-// the step that stores them to LDS minus one (2: plane s+6 at step s; 3:
-// s+7, one register set more, for two workgroups per CU)
-#ifndef PINC_MG_S4_AHEAD
-#define PINC_MG_S4_AHEAD 2
-#endif
-// 1: the phi and rho plane fetches as 16-B x pairs (two loads per thread
-// and plane, the second on the last wave) instead of three 8-B loads
-#ifndef PINC_MG_S4_PAIRS
-#define PINC_MG_S4_PAIRS 1
-#endif
+// rho rides in an LDS ring of its own, fetched like phi and read by each stage
+// from its node's LDS index.  Gathering the rho of each thread's four stages'
+// nodes from memory instead (five colour-strided 8-B gathers per step) was
+// half the launch: 0.168 ms with the gathers, 0.089 ms without, while halving
+// the workgroups per CU costs 5 %; the ring takes 80 KB, two workgroups per CU.
+// The phi and rho plane fetches are 16-B x pairs (two loads per thread and
+// plane, the second on the last wave).
+// Phi and rho planes are fetched this many steps ahead of the step that
+// stores them to LDS minus one (2: plane s+6 at step s; 3: s+7, one register
+// set more, for two workgroups per CU)
+constexpr int kS4Ahead = 2;
 typedef double s4pair __attribute__((ext_vector_type(2)));
 template <int SX, int SY, int NT>
 __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ phiIn, double *__restrict__ phiOut,
@@ -829,25 +623,19 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 	using S = Sweep4c<SX, SY, NT>;
 	constexpr int H = S::H, HX = S::HX, HW = S::HW, PL = S::PL;
 	__shared__ double L[8 * PL];
-#if PINC_MG_S4_RHOLDS
 	__shared__ double Rl[8 * PL];
-#endif
-#if PINC_MG_S4_DIAG & 4
-	__shared__ double padL[38 * 128];
-	if (zPlanes < 0) padL[threadIdx.x] = 1.0, phiOut[threadIdx.x] = padL[(threadIdx.x * 7) % (38 * 128)];
-#endif
 	const int TX = Lp.T[0], TY = Lp.T[1], TZ = Lp.T[2];
 	const long sz = (long)TX * TY;
 	const int ntx = TX / SX, nty = TY / SY;
-	const unsigned tb = xcd_tile(blockIdx.x, gridDim.x);
+	const unsigned tb = blockIdx.x;
 	const int bx = tb % ntx, by = (tb / ntx) % nty, bz = tb / (ntx * nty);
 	const int x0 = bx * SX, y0 = by * SY, z0 = bz * zPlanes;
 	const int tid = threadIdx.x;
 	auto wrapi = [](int i, int T) { return i < 0 ? i + T : (i >= T ? i - T : i); };
 	auto lidx = [](int lx, int ly) { return (unsigned)(ly * HX + (lx & 1) * HW + (lx >> 1)); };
 	auto poff = [&](int gx, int gy) { return (unsigned)(wrapi(gx, TX) + wrapi(gy, TY) * TX) * 8u; };
-	// node j of colour c on a plane of parity P, tile grown by h (the
-	// k_gs_sweep4 enumeration)
+	// node j of colour c on a plane of parity P, tile grown by h (row-major,
+	// rows of even length)
 	auto mknode = [&](int j, int c, int h, int P) {
 		const int hw = (SX + 2 * h) / 2;
 		if (j >= S::nodes(h)) j = 0;  // idle lane: any valid node
@@ -878,9 +666,10 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 	const unsigned oli = lidx(otx + H, oty + H), olxm = lidx(otx + H - 1, oty + H);
 	const unsigned ooff = (unsigned)((x0 + otx) + (y0 + oty) * TX) * 8u;
 	const int oblack0 = (x0 + otx + y0 + oty) & 1;  // black on even planes
-	// phi halo fetch: region element i = tid + NT k (row-major, HX wide);
-	// the third slot's elements on the last threads (those with the fewer
-	// black 1st nodes)
+	// Left over from the 8-B plane fetch (as is S4Node::roff from the rho
+	// gathers) and used by nothing: without these dead computations the
+	// compiler schedules the kernel's prologue differently, so they stay until
+	// a change to this kernel is measured anyway.
 	unsigned foff[3], fli[3];
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
@@ -889,14 +678,10 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 		foff[k] = poff(x0 + i % HX - H, y0 + i / HX - H);
 		fli[k] = lidx(i % HX, i / HX);
 	}
-	const bool f2ok = tid >= 3 * NT - PL;
-	auto at = [](const double *base, unsigned byteOff) {
-		return *(const double *)((const char *)base + byteOff);
-	};
-#if PINC_MG_S4_PAIRS
-	// x pairs of the region (x0 and the region's first column are even, and
-	// so is the level's x extent: a pair never straddles the periodic wrap
-	// and is 16-B aligned): pair q = tid, and q = tid + 64 on the last wave
+	// phi and rho halo fetch, as x pairs of the region (row-major, HX wide; x0
+	// and the region's first column are even, and so is the level's x extent:
+	// a pair never straddles the periodic wrap and is 16-B aligned): pair
+	// q = tid, and q = tid + 64 on the last wave
 	static_assert(PL % 2 == 0 && HX % 2 == 0 && PL / 2 > NT && PL / 2 - NT <= 64, "pair slots");
 	typedef s4pair FV;
 	constexpr int FN = 2;
@@ -913,16 +698,11 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 	auto atp = [](const double *base, unsigned byteOff) {
 		return *(const s4pair *)((const char *)base + byteOff);
 	};
-#else
-	typedef double FV;
-	constexpr int FN = 3;
-#endif
 	auto plane = [&](const double *a, int q) { return a + (long)wrapi(q, TZ) * sz; };
 	// every load below is issued unconditionally (idle lanes and steps past
 	// the end load a valid element they do not use): with loads under a
 	// branch the compiler's vmcnt waits cannot count the newer loads in
 	// flight and wait for the prefetch just issued
-#if PINC_MG_S4_PAIRS
 	auto fetchP = [&](const double *a, int q, FV *f) {
 		const double *b = plane(a, q);
 		f[0] = atp(b, qoff[0]);
@@ -938,66 +718,14 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 	};
 	auto fetch = [&](int q, FV *f) { fetchP(phiIn, q, f); };
 	auto putPhi = [&](int slot, const FV *f) { putP(L, slot, f); };
-#else
-	auto fetch = [&](int q, double *f) {
-#if PINC_MG_S4_DIAG & 2
-		f[0] = f[1] = f[2] = (double)q;
-		return;
-#endif
-		const double *b = plane(phiIn, q);
-		f[0] = at(b, foff[0]);
-		f[1] = at(b, foff[1]);
-		f[2] = at(b, foff[2]);
-	};
-	auto putPhi = [&](int slot, const double *f) {
-		L[slot * PL + fli[0]] = f[0];
-		L[slot * PL + fli[1]] = f[1];
-		if (f2ok) L[slot * PL + fli[2]] = f[2];
-	};
-#endif
-#if PINC_MG_S4_RHOLDS && PINC_MG_S4_PAIRS
 	auto fetchR = [&](int q, FV *f) { fetchP(rho, q, f); };
 	auto putRho = [&](int slot, const FV *f) { putP(Rl, slot, f); };
-#elif PINC_MG_S4_RHOLDS
-	auto fetchR = [&](int q, double *f) {
-#if PINC_MG_S4_DIAG & 1
-		f[0] = f[1] = f[2] = (double)q;
-		return;
-#endif
-		const double *b = plane(rho, q);
-		f[0] = at(b, foff[0]);
-		f[1] = at(b, foff[1]);
-		f[2] = at(b, foff[2]);
-	};
-	auto putRho = [&](int slot, const double *f) {
-		Rl[slot * PL + fli[0]] = f[0];
-		Rl[slot * PL + fli[1]] = f[1];
-		if (f2ok) Rl[slot * PL + fli[2]] = f[2];
-	};
-#endif
-	struct Rho {
-		double r1[2], b1, r2, b2;
-	};
-	// rho of the four stages of step t (t of parity PT)
-	auto fetchRho = [&](int t, int PT, Rho &R) {
-#if PINC_MG_S4_DIAG & 1
-		R.r1[0] = R.r1[1] = R.b1 = R.r2 = R.b2 = (double)t;
-		return;
-#endif
-		const double *b3 = plane(rho, t + 3), *b2p = plane(rho, t + 2), *b0 = plane(rho, t), *bm = plane(rho, t - 2);
-		R.r1[0] = at(b3, r1n[PT ^ 1][0].roff);
-		R.r1[1] = at(b3, r1n[PT ^ 1][1].roff);
-		R.b1 = at(b2p, b1n[PT].roff);
-		R.r2 = at(b0, r2n[PT].roff);
-		R.b2 = at(bm, ooff);
-	};
-	// GS update of node n on ring slot SL (neighbours on slots SM, SP).
-	// PINC_MG_S4_SPLIT: the second read of each neighbour pair goes through
-	// an index the compiler cannot relate to the first (an empty asm), so
-	// the pairs stay two ds_read_b64 (2 LDS cycles each) instead of merging
-	// into ds_read2_b64 / ds_read2st64_b64 (8 cycles, half the rate)
+	// GS update of node n on ring slot SL (neighbours on slots SM, SP).  The
+	// second read of each neighbour pair goes through an index the compiler
+	// cannot relate to the first (an empty asm), so the pairs stay two
+	// ds_read_b64 (2 LDS cycles each) instead of merging into ds_read2_b64 /
+	// ds_read2st64_b64 (8 cycles, half the rate)
 	auto upd = [&](int SL, int SM, int SP, unsigned li, unsigned lxm, double r) {
-#if PINC_MG_S4_SPLIT
 		unsigned ixp = lxm + 1, iyp = li + HX, izp = li;
 		asm volatile("" : "+v"(ixp));
 		asm volatile("" : "+v"(iyp));
@@ -1005,17 +733,12 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 		const double xm = L[SL * PL + lxm], xp = L[SL * PL + ixp];
 		const double ym = L[SL * PL + li - HX], yp = L[SL * PL + iyp];
 		const double zm = L[SM * PL + li], zp = L[SP * PL + izp];
-#else
-		const double xm = L[SL * PL + lxm], xp = L[SL * PL + lxm + 1];
-		const double ym = L[SL * PL + li - HX], yp = L[SL * PL + li + HX];
-		const double zm = L[SM * PL + li], zp = L[SP * PL + li];
-#endif
 		return (1. / 6.) * (xp + xm + yp + ym + zp + zm + r);
 	};
 
-	// prologue: phi z0-4 .. z0-2 into LDS, z0-1 into F[1]; rho of the first
-	// two steps (z0 is a multiple of 8: plane q sits in slot q & 7)
-	constexpr int A = PINC_MG_S4_RHOLDS ? PINC_MG_S4_AHEAD : 2;
+	// prologue: phi z0-4 .. z0-2 into LDS, z0-1 into F[1] (z0 is a multiple
+	// of 8: plane q sits in slot q & 7)
+	constexpr int A = kS4Ahead;
 	static_assert(A == 2 || A == 3, "24-step unroll: register sets rotate by 2 or 3");
 	FV F[A][FN];
 	for (int q = z0 - 4; q <= z0 - 2; q++) {
@@ -1024,7 +747,6 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 	}
 	fetch(z0 - 1, F[1]);
 	if (A == 3) fetch(z0, F[2]);
-#if PINC_MG_S4_RHOLDS
 	// rho planes on the phi ring's schedule: z0-4 .. z0-2 into LDS, z0-1 into
 	// G[1]; plane s+6 fetched and s+5 stored at step s
 	FV G[A][FN];
@@ -1034,14 +756,6 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 	}
 	fetchR(z0 - 1, G[1]);
 	if (A == 3) fetchR(z0, G[2]);
-#else
-	// rho of step k in R[k % 3], loaded two steps ahead; the unroll over 24
-	// steps keeps the rotation in register names (a copy of a set just
-	// loaded would wait for its loads every step)
-	Rho R[3];
-	fetchRho(z0 - 6, 0, R[0]);
-	fetchRho(z0 - 5, 1, R[1]);
-#endif
 	__syncthreads();
 	const int zEnd = z0 + zPlanes;  // outputs z0 .. zEnd-1
 	// steps s = z0-6 .. zEnd+1: zPlanes + 8 of them (a multiple of 24), in
@@ -1053,26 +767,15 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 			const int s = s0 + k;
 			const int P = k & 1;  // parity of s (s0 even)
 			auto sl = [&](int d) { return (2 + k + d) & 7; };
-#if PINC_MG_S4_RHOLDS
 			// rho of a stage's node: its LDS index in the plane's rho slot
 			auto rr = [&](int SL, unsigned li) { return Rl[SL * PL + li]; };
 			// plane s+4+A into set k % A; the set stored below, plane s+5,
 			// was fetched A-1 steps ago into set (k + 1) % A
 			fetch(s + 4 + A, F[k % A]);
 			fetchR(s + 4 + A, G[k % A]);
-#else
-			Rho &RA = R[k % 3];
-			// two steps ahead of their use (the last step's loads are unused)
-			fetch(s + 6, F[P]);
-			fetchRho(s + 2, P, R[(k + 2) % 3]);
-#endif
 			if (s + 3 <= zEnd + 2) {  // red, 1st iteration, plane s+3 (parity P^1)
 				const S4Node &a = r1n[P ^ 1][0], &b = r1n[P ^ 1][1];
-#if PINC_MG_S4_RHOLDS
 				const double ra = rr(sl(3), a.li), rb = rr(sl(3), b.li);
-#else
-				const double ra = RA.r1[0], rb = RA.r1[1];
-#endif
 				const double va = upd(sl(3), sl(2), sl(4), a.li, a.lxm, ra);
 				double vb = 0;
 				if (r1second) vb = upd(sl(3), sl(2), sl(4), b.li, b.lxm, rb);
@@ -1081,37 +784,23 @@ __global__ __launch_bounds__(NT) void k_gs_sweep4c(const double *__restrict__ ph
 			}
 			if (s >= z0 - 1 && s <= zEnd && r2ok) {  // red, 2nd, plane s
 				const S4Node &a = r2n[P];
-#if PINC_MG_S4_RHOLDS
 				L[sl(0) * PL + a.li] = upd(sl(0), sl(-1), sl(1), a.li, a.lxm, rr(sl(0), a.li));
-#else
-				L[sl(0) * PL + a.li] = upd(sl(0), sl(-1), sl(1), a.li, a.lxm, RA.r2);
-#endif
 			}
 			{  // black, 2nd, plane s-2: out.  Before the first output plane the
 			   // store goes to plane z0, rewritten with its value later (the
 			   // store is unconditional for the same reason as the loads)
 				double v = L[sl(-2) * PL + oli];
-#if PINC_MG_S4_RHOLDS
 				if (oblack0 ^ P) v = upd(sl(-2), sl(-3), sl(-1), oli, olxm, rr(sl(-2), oli));
-#else
-				if (oblack0 ^ P) v = upd(sl(-2), sl(-3), sl(-1), oli, olxm, RA.b2);
-#endif
 				*(double *)((char *)plane(phiOut, s - 2 >= z0 ? s - 2 : z0) + ooff) = v;
 			}
 			__syncthreads();
 			if (s + 2 >= z0 - 2 && s + 2 <= zEnd + 1 && b1ok) {  // black, 1st, plane s+2
 				const S4Node &a = b1n[P];
-#if PINC_MG_S4_RHOLDS
 				L[sl(2) * PL + a.li] = upd(sl(2), sl(1), sl(3), a.li, a.lxm, rr(sl(2), a.li));
-#else
-				L[sl(2) * PL + a.li] = upd(sl(2), sl(1), sl(3), a.li, a.lxm, RA.b1);
-#endif
 			}
 			// phi s+5 into the slot of s-3 (last read by the black output above)
 			putPhi(sl(5), F[(k + 1) % A]);
-#if PINC_MG_S4_RHOLDS
 			putRho(sl(5), G[(k + 1) % A]);  // (rho s-3: last read by the black output a step ago)
-#endif
 			__syncthreads();
 		}
 	}
@@ -1409,8 +1098,13 @@ struct SmallArgs {
 	double tol;        // stop once the RMS residual is <= tol (or not finite)
 };
 
+// Diagnostic build switch, kept: 1 puts the first cycle's phase times (100 MHz
+// ticks) in out[2..] instead of the history (read by tools/small_solve_diag.py).
+// At 0 the stamps compile to nothing, but deleting them changes the register
+// allocation of the SPEC = false instances (two more SGPR spills), so the hook
+// goes only with a change to this kernel that is measured.
 #ifndef PINC_SMALL_DIAG
-#define PINC_SMALL_DIAG 0  // 1: the first cycle's phase times (100 MHz ticks) in out[2..] instead of the history
+#define PINC_SMALL_DIAG 0
 #endif
 
 // (phi and res not __restrict__: other waves of the workgroup read what a
@@ -1975,8 +1669,7 @@ extern "C" int pinc_hip_resid_restrict(const double *phi, const double *rho, dou
 	if (8 * npts(Lc) >= (1L << 31)) return set_error(hipErrorInvalidValue, "resid_restrict: level too large");
 	hipStream_t st = (hipStream_t)stream;
 	const unsigned nb = blocks_for(npts(Lc));
-	const bool pairs = PINC_MG_RR_PAIRS &&
-	                   !((reinterpret_cast<unsigned long>(phi) | reinterpret_cast<unsigned long>(rho)) & 15);
+	const bool pairs = !((reinterpret_cast<unsigned long>(phi) | reinterpret_cast<unsigned long>(rho)) & 15);
 	if (pairs && hw3d)
 		hipLaunchKernelGGL(k_resid_restrict3p<true>, dim3(nb), dim3(kThreads), 0, st, phi, rho, coarse, Lc, scale);
 	else if (pairs)
@@ -2040,7 +1733,7 @@ extern "C" int pinc_hip_residual_sumsq(const double *phi, const double *rho, pin
 	hipStream_t st = (hipStream_t)stream;
 	unsigned nb = blocks_for(npts(L));
 	*nBlocks = (int)nb;
-	if (L.nd == 3 && PINC_MG_NORM_PAIRS && L.T[0] % 2 == 0 &&
+	if (L.nd == 3 && L.T[0] % 2 == 0 &&
 	    !((reinterpret_cast<unsigned long>(phi) | reinterpret_cast<unsigned long>(rho)) & 15)) {
 		nb = blocks_for(npts(L) / 2);
 		*nBlocks = (int)nb;
@@ -2108,18 +1801,13 @@ extern "C" int pinc_hip_gs_sweep2x(const double *phiIn, double *phiOut, const do
 	long cols = (long)(L.T[0] / 32) * (L.T[1] / 8);
 	int zp = 16;
 	for (int z = 64; z > 16; z /= 2)
-		if (L.T[2] % z == 0 && cols * (L.T[2] / z) >= 1024 && (!PINC_MG_SWEEP4C || (z + 8) % 24 == 0)) {
+		if (L.T[2] % z == 0 && cols * (L.T[2] / z) >= 1024 && (z + 8) % 24 == 0) {
 			zp = z;  // k_gs_sweep4c marches in blocks of 24 steps: zPlanes + 8 = 24 m
 			break;
 		}
 	unsigned nb = (unsigned)(cols * (L.T[2] / zp));
-#if PINC_MG_SWEEP4C
 	hipLaunchKernelGGL((k_gs_sweep4c<32, 8, 256>), dim3(nb), dim3(256), 0, (hipStream_t)stream, phiIn, phiOut, rho, L,
 	                   zp);
-#else
-	hipLaunchKernelGGL((k_gs_sweep4<32, 8, 256>), dim3(nb), dim3(256), 0, (hipStream_t)stream, phiIn, phiOut, rho, L,
-	                   zp);
-#endif
 	return check_launch("gs_sweep2x");
 }
 

@@ -403,9 +403,6 @@ __device__ __forceinline__ int wave_reduce_i(int v, int id, Op op) {
 	v = op(v, dpp_i<0x143, 0xc>(id, v));  // row_bcast:31 into rows 2, 3
 	return __builtin_amdgcn_readlane(v, 63);
 }
-#ifndef PINC_DPP_REDUCE
-#define PINC_DPP_REDUCE 1
-#endif
 // fp64 wave sum, the same DPP pattern on the two halves of each partner
 // value (a fixed tree: deterministic); the total in every lane's return
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -426,7 +423,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 	const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, 63), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), 63);
 	return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-#if PINC_DPP_REDUCE
 __device__ __forceinline__ int wave_min_i(int v) {
 	return wave_reduce_i(v, INT32_MAX, [](int a, int b) { return min(a, b); });
 }
@@ -436,19 +432,6 @@ __device__ __forceinline__ int wave_max_i(int v) {
 __device__ __forceinline__ int wave_sum_i(int v) {
 	return wave_reduce_i(v, 0, [](int a, int b) { return a + b; });
 }
-#else
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-	return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-	return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) { return wave_sum(v); }
-#endif
 
 template <int ND, bool V3D>
 __device__ __forceinline__ void cic_weights(const double *dec, const double *comp, double *w) {
@@ -1127,17 +1110,14 @@ __global__ __launch_bounds__(kThreads) void k_sort_count(const double *__restric
 // push reserves per brick; immigrants joining the counts, or counts made
 // without a counting push)
 // Cell a particle is sorted by in the in-push sort (the counting push, the
-// brick counts and the sorting push must agree): with PINC_SORT_AHEAD (the
-// default) the cell of x + v, where the next push's drift takes it before its
-// kick, so that a sorting push's output lies in the bricks it was ranked
-// into (sorted by the input cell x, the output of every block spread one
-// cell around its bricks: E and charge boxes 6 x 6 x 3 cells instead of
-// 4 x 4 x 1).  Clamped to the grid like every key (a particle that wraps
-// through a periodic face is placed at the face it left: order only).
-#ifndef PINC_SORT_AHEAD
-#define PINC_SORT_AHEAD 1
-#endif
-__device__ __forceinline__ int sort_cell(double x, double v) { return PINC_SORT_AHEAD ? (int)(x + v) : (int)x; }
+// brick counts and the sorting push must agree): the cell of x + v, where
+// the next push's drift takes it before its kick, so that a sorting push's
+// output lies in the bricks it was ranked into (sorted by the input cell x,
+// the output of every block spread one cell around its bricks: E and charge
+// boxes 6 x 6 x 3 cells instead of 4 x 4 x 1).  Clamped to the grid like
+// every key (a particle that wraps through a periodic face is placed at the
+// face it left: order only).
+__device__ __forceinline__ int sort_cell(double x, double v) { return (int)(x + v); }
 
 template <int ND>
 __global__ __launch_bounds__(kThreads) void k_count_bricks(const double *__restrict__ x0,
@@ -1433,185 +1413,41 @@ struct PushArgs {
 		tsub = now;                                                           \
 	}
 
-// same-cell groups of at least kPushGroupMin lanes (at most kPushGroups of
-// them per wave and item) are summed across the wave before the LDS add
-// (6: measured at C4, 30.34 ms per species launch against 30.84 with 2;
-// smaller groups are cheaper as direct LDS adds than as wave reductions)
-#ifndef PINC_PUSH_GROUP_MIN
-#define PINC_PUSH_GROUP_MIN 6
-#endif
-#ifndef PINC_PUSH_GROUPS
-#define PINC_PUSH_GROUPS 4
-#endif
-constexpr int kPushGroupMin = PINC_PUSH_GROUP_MIN;
-// diagnostics only (timing by elimination, wrong results): bit 0 skips the
-// deposit, bit 1 the E staging and gather, bit 2 the flush
-#ifndef PINC_PUSH_SKIP
-#define PINC_PUSH_SKIP 0
-#endif
-// deposit into per-lane-group copies of the LDS charge box (lane & (nc-1)
-// picks the copy, nc <= PINC_PUSH_COPIES copies as the box allows) with
-// plain LDS atomics, instead of same-cell wave reductions (0).  Measured at
-// C4 (mean over the sort cycle): 0 copies 29.6 ms per species launch,
-// 2 copies 30.0, 4 copies 28.2, 8 copies 28.2 -- a sorted wave's lanes
-// mostly share one cell, and 8 copies cut the same-address conflicts of
-// each ds_add_f64 to 8-way for ~60 fewer VALU instructions per particle
-// than the reduction.  (Tried and rejected the same day: whole-chunk
-// launches without per-element conditions, 43 ms, spills; 2 items per
-// thread at 4-5 waves/SIMD, 31-32 ms; 512-thread blocks, 35.8 ms.)
-#ifndef PINC_PUSH_COPIES
-#define PINC_PUSH_COPIES 8
-#endif
-// 1: a thread's particles are consecutive in memory, with plain loads and
-// stores (measured at C4, mean over the sort cycle, per species launch:
-// 27.1 ms against 28.3 for lane pairs 512 apart with nontemporal access;
-// this pattern with nontemporal loads and stores 42 ms, nontemporal stores
-// only 33.7, nontemporal loads only 30.1 -- each wave instruction covers
-// every other 16 B of 2 KB and the next one the rest, which must meet in
-// L2; PMC traffic 122 GB per launch against 110 GB)
-#ifndef PINC_PUSH_CONSEC
-#define PINC_PUSH_CONSEC 1
-#endif
-// lane pairs (PINC_PUSH_CONSEC 0): nontemporal particle loads and stores
-#ifndef PINC_PUSH_NT
-#define PINC_PUSH_NT 0
-#endif
-// 1 (with PINC_PUSH_CONSEC): a full block's particle loads and stores are
-// contiguous per wave instruction (lane l: 16-B pair l, then pair 64 + l of
-// the wave's 256 particles) and adjacent lanes swap one pair each (DPP), so
-// that a thread still holds four consecutive particles: even lane 2k those
-// at 4k, odd lane 2k + 1 those at 128 + 4k.  The mapping where a thread
-// loads its own four (every other 16 B of 2 KB per instruction) copies at
-// 5.69 TB/s on this chip against 6.13 TB/s contiguous
-// (profiles/r06b_copy_probe3_lane_mapping.jsonl)
-#ifndef PINC_PUSH_XCH
-#define PINC_PUSH_XCH 2
-#endif
-// (PINC_PUSH_XCH 2, full blocks) bit 0: nontemporal particle loads, bit 1:
-// nontemporal particle stores (every wave instruction covers whole lines).
-// Both (3): plain push 19.63 -> 19.06 ms per species launch at C4, loads
-// alone 19.39, stores alone 19.30 (profiles/r06g_push_nontemporal_ab.txt);
-// with the round-5 mapping, where two instructions shared each line,
-// nontemporal access was slower (27.1 -> 30.1-42 ms, round 2)
-#ifndef PINC_PUSH_XCH_NT
-#define PINC_PUSH_XCH_NT 3
-#endif
-// 1: the counting push adds a thread's same-brick items with one plain LDS
-// atomic instead of wave-aggregated adds per item (counting push 22.36 ->
-// 21.79 ms at C4, plain push unchanged, no spill with the lane exchange's
-// registers; profiles/r06i_count_runs_sort_nt_ab.txt)
-#ifndef PINC_PUSH_COUNT_RUNS
-#define PINC_PUSH_COUNT_RUNS 1
-#endif
-#ifndef PINC_PUSH_RHO_LDS
-#define PINC_PUSH_RHO_LDS 2048
-#endif
-constexpr int kRhoLds = PINC_PUSH_COPIES ? PINC_PUSH_RHO_LDS : 1024;
-
-constexpr int kPushGroups = PINC_PUSH_GROUPS;
+// The deposit goes into per-lane-group copies of the LDS charge box (lane &
+// (nc-1) picks the copy, nc <= kPushCopies copies as the box allows) with
+// plain LDS atomics.  Measured at C4 (mean over the sort cycle): same-cell
+// wave reductions and no copies 29.6 ms per species launch, 2 copies 30.0,
+// 4 copies 28.2, 8 copies 28.2 -- a sorted wave's lanes mostly share one
+// cell, and 8 copies cut the same-address conflicts of each ds_add_f64 to
+// 8-way for ~60 fewer VALU instructions per particle than the reduction.
+// (Tried and rejected the same day: whole-chunk launches without per-element
+// conditions, 43 ms, spills; 2 items per thread at 4-5 waves/SIMD, 31-32 ms;
+// 512-thread blocks, 35.8 ms.)
+constexpr int kPushCopies = 8;
+constexpr int kRhoLds = 2048;  // charge box and its copies (doubles of LDS; the sorting push keeps 1024)
 // 8 waves x 4 particles per thread per PINC_CHUNK block: fewer live VGPRs
-// (px) than 4 waves x 8, so more waves per SIMD hide the gather latency
-#ifndef PINC_PUSH_ITEMS
-#define PINC_PUSH_ITEMS 4
-#endif
-#ifndef PINC_PUSH_WPE
-#define PINC_PUSH_WPE 4
-#endif
-// 2 (default): pieces of PINC_PUSH_XCD_PIECE chunks round-robin over the
-// XCDs (C4: step 55.39 -> 55.07 ms; the contiguous eighths of 1 left the XCD
-// holding the top z tiles 1.2 ms behind the others on the electrons)
-#ifndef PINC_PUSH_XCD
-#define PINC_PUSH_XCD 2
-#endif
-#ifndef PINC_PUSH_XCD_PIECE
-#define PINC_PUSH_XCD_PIECE 64
-#endif
-#ifndef PINC_PUSH_THREADS
-#define PINC_PUSH_THREADS 256
-#endif
-// 1: the sorting push orders each brick's run by cell (per (brick, cell)
-// counters for blocks whose brick box holds at most kCellRankBricks bricks of
-// at most 16 cells), so repeated sorts keep a brick's particles cell-contiguous
-#ifndef PINC_SORT_CELLRANK
-#define PINC_SORT_CELLRANK 1
-#endif
+// (px) than 4 waves x 8, so more waves per SIMD hide the gather latency.
+// A thread's particles are consecutive in memory (measured at C4, mean over
+// the sort cycle, per species launch: 27.1 ms against 28.3 for lane pairs 512
+// apart), and a full block's particle loads and stores are contiguous per
+// wave instruction, rows of 16 lanes swapping halves (k_push, phase A): a
+// mapping where a thread loads its own four (every other 16 B of 2 KB per
+// instruction) copies at 5.69 TB/s on this chip against 6.13 TB/s contiguous
+// (profiles/r06b_copy_probe3_lane_mapping.jsonl).  Every wave instruction of
+// a full block covers whole lines, so its particle loads and stores are
+// nontemporal: plain push 19.63 -> 19.06 ms per species launch at C4, loads
+// alone 19.39, stores alone 19.30 (profiles/r06g_push_nontemporal_ab.txt).
+constexpr int kPushThreads = 256;
+constexpr int kPushItems = 4;  // particles per thread, consecutive
+constexpr int kPushWavesPerEu = 4;  // k_push's amdgpu_waves_per_eu
+constexpr int kPushChunk = kPushThreads * kPushItems;  // particles per block (PINC_CHUNK / 2)
+// chunks per piece of push_chunk_of's round-robin over the XCDs
+constexpr unsigned kPushXcdPiece = 64;
+// The sorting push orders each brick's run by cell (per (brick, cell) counters
+// for blocks whose brick box holds at most kCellRankBricks bricks of at most
+// 16 cells), so repeated sorts keep a brick's particles cell-contiguous
 constexpr int kCellRankBricks = 64;
-// wave priority (s_setprio) of a block's particle-load phase (> 0), or of
-// everything after it (< 0); 0: off
-#ifndef PINC_PUSH_PRIO
-#define PINC_PUSH_PRIO 0
-#endif
-// 1: per-item periodic images only in blocks that straddle a boundary (k_push)
-#ifndef PINC_PUSH_IMG_GATE
-#define PINC_PUSH_IMG_GATE 1
-#endif
-// 1: the cell-change statistic from the pre-move cell, the frame test only
-// for particles that leave the centre (k_push)
-#ifndef PINC_PUSH_LEAN
-#define PINC_PUSH_LEAN 1
-#endif
-constexpr int kPushThreads = PINC_PUSH_THREADS;
-constexpr int kPushItems = PINC_PUSH_ITEMS;  // particles per thread, in lane-contiguous pairs
-constexpr int kPushChunk = kPushThreads * kPushItems;  // particles per block (PINC_CHUNK / 2 by default)
 static_assert(kPushChunk >= PINC_CHUNK / 8 && PINC_CHUNK % kPushChunk == 0, "kePartial holds PINC_CHUNK/8 per chunk");
-
-// double-precision lane exchange helpers on the two 32-bit halves
-__device__ __forceinline__ void permlane32_swap(double &a, double &b) {
-	// v_permlane32_swap_b32: lanes 32..63 of a <-> lanes 0..31 of b
-	unsigned long long ua = __double_as_longlong(a), ub = __double_as_longlong(b);
-	auto lo = __builtin_amdgcn_permlane32_swap((unsigned)ua, (unsigned)ub, false, false);
-	auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32), false, false);
-	a = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0]));
-	b = __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
-}
-__device__ __forceinline__ void permlane16_swap(double &a, double &b) {
-	// v_permlane16_swap_b32: odd rows of a <-> even rows of b (rows of 16 lanes)
-	unsigned long long ua = __double_as_longlong(a), ub = __double_as_longlong(b);
-	auto lo = __builtin_amdgcn_permlane16_swap((unsigned)ua, (unsigned)ub, false, false);
-	auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32), false, false);
-	a = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0]));
-	b = __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-	unsigned long long u = __double_as_longlong(v);
-	unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)u, CTRL, 0xf, 0xf, false);
-	unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-	return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-constexpr int kDppRowRor8 = 0x128, kDppHalfMirror = 0x141, kDppQuadXor2 = 0x4e, kDppQuadXor1 = 0xb1;
-
-// sum of r[0..7] over the 64 lanes, transposed: afterwards lane l holds the
-// total of corner 4*b5 + 2*b4 + b3 (b = bits of l) in lanes with (l & 7) == 0
-__device__ __forceinline__ double wave_reduce8(double *r) {
-	const int lane = threadIdx.x & 63;
-	// lanes 0..31 gather corners 0..3, lanes 32..63 corners 4..7
-	double a[4];
-#pragma unroll
-	for (int i = 0; i < 4; i++) {
-		double x = r[i], y = r[i + 4];
-		permlane32_swap(x, y);
-		a[i] = x + y;
-	}
-	// rows 0,2 gather a[0..1], rows 1,3 a[2..3]
-	double b[2];
-#pragma unroll
-	for (int i = 0; i < 2; i++) {
-		double x = a[i], y = a[i + 2];
-		permlane16_swap(x, y);
-		b[i] = x + y;
-	}
-	// half rows: lanes with bit 3 clear keep b[0], set keep b[1]
-	const bool h3 = lane & 8;
-	double send = h3 ? b[0] : b[1];
-	double keep = h3 ? b[1] : b[0];
-	double c = keep + dpp<kDppRowRor8>(send);
-	// total over the 8 lanes of each group
-	c += dpp<kDppHalfMirror>(c);
-	c += dpp<kDppQuadXor2>(c);
-	c += dpp<kDppQuadXor1>(c);
-	return c;
-}
 
 // storage offsets (in nodes, 32-bit) of padded node coordinates j and j+1
 // along dimension d of the slab (periodic x/y stored without ghosts)
@@ -1689,14 +1525,8 @@ __device__ __forceinline__ Images make_images(const Geo32 &G, int wrapMask, cons
 // 539 E nodes, 1053 charge nodes); with 384 and 1024 such chunks -- a
 // quarter of them -- gathered E and added charge through global memory.
 constexpr int kRhoBoxCap = 1024;
-#ifndef PINC_PUSH_EBOX
-#define PINC_PUSH_EBOX 768
-#endif
-constexpr int kEBoxCapPlain = PINC_PUSH_EBOX;
-#ifndef PINC_PUSH_SORT_EBOX
-#define PINC_PUSH_SORT_EBOX PINC_PUSH_EBOX
-#endif
-constexpr int kEBoxCapSort = PINC_PUSH_SORT_EBOX;
+constexpr int kEBoxCapPlain = 768;
+constexpr int kEBoxCapSort = 768;
 constexpr int kInCellCap = 256;
 constexpr int kOutCellCap = 512;
 
@@ -1717,12 +1547,6 @@ struct Box {
 		for (int d = 0; d < nd; d++) ok = ok && c[d] >= lo[d] && c[d] < lo[d] + n[d];
 		return ok;
 	}
-	__device__ __forceinline__ void coords(int l, int *c, int nd) const {
-		for (int d = 0; d < nd; d++) {
-			c[d] = lo[d] + l % n[d];
-			l /= n[d];
-		}
-	}
 };
 // Box coordinates of linear index l < vol without integer division: the
 // block-uniform reciprocals of the extents (box_rcp) and one float multiply
@@ -1738,15 +1562,7 @@ __device__ __forceinline__ BoxRcp box_rcp(const Box &b) {
 	for (int d = 0; d < 3; d++) q.r[d] = 1.0f / (float)b.n[d];
 	return q;
 }
-#ifndef PINC_PUSH_FASTDIV
-#define PINC_PUSH_FASTDIV 1
-#endif
 __device__ __forceinline__ void box_coords(const Box &b, const BoxRcp &q, int l, int *c, int nd) {
-#if !PINC_PUSH_FASTDIV
-	(void)q;
-	b.coords(l, c, nd);
-	return;
-#endif
 #pragma unroll
 	for (int d = 0; d < 3; d++) {
 		if (d >= nd) break;
@@ -1763,10 +1579,7 @@ __device__ __forceinline__ void box_coords(const Box &b, const BoxRcp &q, int l,
 // entries: each dimension first to kBoxReach cells either side of the mean
 // cell mid, then the widest one cell at a time from its side farther from mid
 // (block-uniform; vol 0 if even a single cell does not fit).
-#ifndef PINC_PUSH_REACH
-#define PINC_PUSH_REACH 8
-#endif
-constexpr int kBoxReach = PINC_PUSH_REACH;
+constexpr int kBoxReach = 8;
 __device__ __forceinline__ Box make_box(const int *clo, const int *chi, const int *mid, int grow_lo, int grow_hi,
                                         int nd, int cap) {
 	int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
@@ -1795,35 +1608,6 @@ __device__ __forceinline__ Box make_box(const int *clo, const int *chi, const in
 	}
 	b.vol = (v <= cap && v > 0) ? (int)v : 0;
 	return b;
-}
-
-// LDS counter add of 1 per active lane at ctr[idx], aggregated over the
-// lanes that share an index: the two largest groups (first and last pending
-// lane's index) take one atomic each, the rest add individually.  Returns the
-// lane's rank (old value + rank among its group) when RET.
-template <bool RET>
-__device__ __forceinline__ int lds_agg_add(int *ctr, int idx, bool active) {
-	const int lane = threadIdx.x & 63;
-	unsigned long long pend = __ballot(active);
-	int mine = 0;
-#pragma unroll 1
-	for (int grp = 0; grp < 2 && pend; grp++) {
-		int leader = grp ? 63 - __clzll((long long)pend) : __ffsll((long long)pend) - 1;
-		int li = __shfl(idx, leader, 64);
-		unsigned long long m = __ballot(active && idx == li) & pend;
-		pend &= ~m;
-		int b = 0;
-		if (lane == leader) b = atomicAdd(&ctr[li], __popcll(m));
-		if (RET) {
-			b = __shfl(b, leader, 64);
-			if ((m >> lane) & 1ull) mine = b + __popcll(m & lanemask_lt());
-		}
-	}
-	if ((pend >> lane) & 1ull) {
-		int b = atomicAdd(&ctr[idx], 1);
-		if (RET) mine = b;
-	}
-	return mine;
 }
 
 // sort key of integer cell coordinates (tile_key's order)
@@ -1936,38 +1720,31 @@ __device__ __forceinline__ int brick_key(const TileGeo &tg, const BrickBox &bb, 
 
 typedef double dvec2 __attribute__((ext_vector_type(2)));
 
-// chunk of push block b of nb.  PINC_PUSH_XCD: consecutive chunks (the same
-// cell tiles after a sort: shared E nodes and rho atomics) on one XCD's L2.
+// chunk of push block b of nb: consecutive chunks (the same cell tiles after
+// a sort: shared E nodes and rho atomics) on one XCD's L2.
 // Blocks are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md,
 // workgroup dispatch), so block b runs on XCD b % 8; the map is a bijection
 // for any grid size and only a placement hint, never needed for
 // correctness.  (Host and device: the push trace attributes chunks to XCDs
 // with it, pinc_hip_push_xcd_of_chunk.)
 __host__ __device__ __forceinline__ unsigned push_chunk_of(unsigned nb, unsigned b) {
-#if PINC_PUSH_XCD == 2
-	// pieces of PINC_PUSH_XCD_PIECE consecutive chunks dealt round-robin over
+	// pieces of kPushXcdPiece consecutive chunks dealt round-robin over
 	// the XCDs (the tail beyond whole rounds in order): every XCD gets pieces
 	// from every part of the array, e.g. both z faces' tiles, where wrapped
-	// particles make blocks slower
-	constexpr unsigned P = PINC_PUSH_XCD_PIECE;
+	// particles make blocks slower (C4: step 55.39 -> 55.07 ms against
+	// contiguous eighths, which left the XCD holding the top z tiles 1.2 ms
+	// behind the others on the electrons)
+	constexpr unsigned P = kPushXcdPiece;
 	const unsigned F = nb / (8u * P) * (8u * P);
 	if (b >= F) return b;
 	const unsigned x = b & 7u, y = b >> 3;
 	return ((y / P) * 8u + x) * P + (y % P);
-#elif PINC_PUSH_XCD
-	const unsigned x = b & 7u, y = b >> 3;
-	const unsigned q = nb >> 3, r = nb & 7u;
-	return x * q + (x < r ? x : r) + y;
-#else
-	(void)nb;
-	return b;
-#endif
 }
 
 // OBJ: the object test of the fused collection (separate instances, so the
 // plain push carries none of its code)
 template <int ND, bool V3D, bool KICK, bool SORT, bool OBJ = false>
-__global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PINC_PUSH_WPE))) void k_push(PushArgs a) {
+__global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(kPushWavesPerEu))) void k_push(PushArgs a) {
 	constexpr int NC = 1 << ND;
 	constexpr int NW = kPushThreads / 64;
 	// the sorting push keeps its LDS at 40 KB (4 blocks per CU): fewer copies
@@ -1988,46 +1765,24 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	__shared__ int wmov[NW];
 	// sorting push, per item: its rank code (phase C) and its flag (phase D)
 	__shared__ int rlL[SORT ? kPushChunk : 1];
-	// sorting push with PINC_SORT_CELLRANK: counters, then exclusive offsets,
-	// of (brick, cell in brick)
-	__shared__ int ccL[(SORT && PINC_SORT_CELLRANK) ? kCellRankBricks * 16 : 1];
+	// sorting push: counters, then exclusive offsets, of (brick, cell in brick)
+	__shared__ int ccL[SORT ? kCellRankBricks * 16 : 1];
 	__shared__ unsigned char stageF[SORT ? kPushChunk : 1];
 	const Geo32 G = make_geo32(a.g);
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	// chunk of this block (push_chunk_of: XCD-aware placement)
 	const unsigned chunk = push_chunk_of(gridDim.x, blockIdx.x);
 	const long base = (long)chunk * kPushChunk;
-	// item k of a thread: particles in lane-contiguous pairs (16-B loads and
-	// stores, 1 KiB per wave instruction), pair k/2 of the thread
-#if PINC_PUSH_CONSEC && PINC_PUSH_XCH == 2
-	// the kPushItems particles of a thread are consecutive, so a thread's
-	// particles mostly share a cell and their charge is summed in the thread
-	// before the LDS adds; rows of 16 lanes swap halves so that full blocks
-	// load and store contiguously (PINC_PUSH_XCH): row r of a wave holds the
-	// 64 consecutive particles at {0, 128, 64, 192}[r], lane i of it those
-	// at 4i of them
+	// item k of a thread: the kPushItems particles of a thread are
+	// consecutive, so a thread's particles mostly share a cell and their
+	// charge is summed in the thread before the LDS adds; rows of 16 lanes swap
+	// halves so that full blocks load and store contiguously: row r of a wave
+	// holds the 64 consecutive particles at {0, 128, 64, 192}[r], lane i of it
+	// those at 4i of them
 	static_assert(kPushItems == 4 && kPushThreads % 64 == 0, "lane exchange: four items per thread");
 	auto item = [&](int k) -> long {
 		return base + (long)(wv * 256 + ((lane >> 4) & 1) * 128 + (lane >> 5) * 64 + (lane & 15) * 4 + k);
 	};
-#elif PINC_PUSH_CONSEC && PINC_PUSH_XCH
-	// the kPushItems particles of a thread are consecutive, so a thread's
-	// particles mostly share a cell and their charge is summed in the thread
-	// before the LDS adds; lane pairs swap halves so that full blocks load
-	// and store contiguously (PINC_PUSH_XCH)
-	static_assert(kPushItems == 4 && kPushThreads % 64 == 0, "lane exchange: four items per thread");
-	auto item = [&](int k) -> long {
-		return base + (long)(wv * 256 + (lane & 1) * 128 + (lane >> 1) * 4 + k);
-	};
-#elif PINC_PUSH_CONSEC
-	// the kPushItems particles of a thread are consecutive (two 16-B loads per
-	// array and thread: a wave instruction covers every other 16 B of 2 KB,
-	// the next one the rest, through L2), so a thread's particles mostly share
-	// a cell and their charge is summed in the thread before the LDS adds
-	auto item = [&](int k) -> long { return base + (long)(kPushItems * threadIdx.x + k); };
-#else
-	auto item = [&](int k) -> long { return base + (long)((k >> 1) * (2 * kPushThreads) + 2 * threadIdx.x + (k & 1)); };
-#endif
 	// pairs are 16-B aligned when every species array is (the species
 	// offset iStart is even); otherwise one 8-B access per particle
 	bool al = true;
@@ -2037,9 +1792,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		              reinterpret_cast<unsigned long>(a.xo[d]) | reinterpret_cast<unsigned long>(a.vo[d])) & 15);
 
 	unsigned long long tsub = 0;  // (trace mode: thread 0's last timestamp)
-	// (PINC_PUSH_PRIO: a block's waves issue their particle loads at raised
-	// wave priority, so the memory pipe is fed before older blocks' compute)
-	if (PINC_PUSH_PRIO > 0) __builtin_amdgcn_s_setprio(PINC_PUSH_PRIO);
 	PUSH_TS(0);
 	// ---- phase A: load every item, cell box of the input positions (periodic
 	// images nearest to the cell of the block's first item)
@@ -2053,14 +1805,10 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	double p[kPushItems][ND], vv[kPushItems][ND];
 	unsigned valid = 0;
 	static_assert(kPushItems % 2 == 0, "items come in pairs");
-#if PINC_PUSH_CONSEC && PINC_PUSH_XCH
 	// a full block of aligned arrays: two contiguous 16-B loads per array and
-	// thread (wave pairs lane and 64 + lane), then the odd lane's first pair
-	// and the even lane's second pair change places (quad_perm [1,0,3,2])
+	// thread
 	const bool full = al && base + kPushChunk <= a.n;
-	const bool odd = lane & 1;
-	auto swap_adj = [](dvec2 v) -> dvec2 { return dvec2{dpp<kDppQuadXor1>(v.x), dpp<kDppQuadXor1>(v.y)}; };
-	// (XCH 2) lane l loads pair pi(l) and 64 + pi(l) of the wave's 128: rows 0
+	// lane l loads pair pi(l) and 64 + pi(l) of the wave's 128: rows 0
 	// and 1 (2 and 3) interleave pairs 0..31 (32..63) even/odd, so the row
 	// swap (v_permlane16_swap: odd rows of the first <-> even rows of the
 	// second) leaves each lane two consecutive pairs; every wave instruction
@@ -2078,14 +1826,11 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		u = __builtin_bit_cast(dvec2, A);
 		w = __builtin_bit_cast(dvec2, B);
 	};
-	(void)pi_lane;
-	(void)rowswap;
-	if (full && PINC_PUSH_XCH == 2) {
+	if (full) {
 		valid = (1u << kPushItems) - 1;
 		const long q0 = base + wv * 256 + 2 * pi_lane(lane);
 		auto ld = [](const double *ptr) -> dvec2 {
-			if (PINC_PUSH_XCH_NT & 1) return __builtin_nontemporal_load(reinterpret_cast<const dvec2 *>(ptr));
-			return *reinterpret_cast<const dvec2 *>(ptr);
+			return __builtin_nontemporal_load(reinterpret_cast<const dvec2 *>(ptr));
 		};
 #pragma unroll
 		for (int d = 0; d < ND; d++) {
@@ -2104,29 +1849,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 			vv[2][d] = v1.x;
 			vv[3][d] = v1.y;
 		}
-	} else if (full) {
-		valid = (1u << kPushItems) - 1;
-		const long q0 = base + wv * 256 + 2 * lane;  // the wave's pair `lane`; pair 64 + lane 128 later
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			const dvec2 x0 = *reinterpret_cast<const dvec2 *>(a.xi[d] + q0);
-			const dvec2 x1 = *reinterpret_cast<const dvec2 *>(a.xi[d] + q0 + 128);
-			const dvec2 v0 = *reinterpret_cast<const dvec2 *>(a.vi[d] + q0);
-			const dvec2 v1 = *reinterpret_cast<const dvec2 *>(a.vi[d] + q0 + 128);
-			const dvec2 xr = swap_adj(odd ? x0 : x1), vr = swap_adj(odd ? v0 : v1);
-			const dvec2 xa = odd ? xr : x0, xb = odd ? x1 : xr;
-			const dvec2 va = odd ? vr : v0, vb = odd ? v1 : vr;
-			p[0][d] = xa.x;
-			p[1][d] = xa.y;
-			p[2][d] = xb.x;
-			p[3][d] = xb.y;
-			vv[0][d] = va.x;
-			vv[1][d] = va.y;
-			vv[2][d] = vb.x;
-			vv[3][d] = vb.y;
-		}
 	} else
-#endif
 #pragma unroll
 	for (int k = 0; k < kPushItems; k += 2) {
 		const long i = item(k);
@@ -2135,14 +1858,8 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 #pragma unroll
 		for (int d = 0; d < ND; d++) {
 			if (ok1 && al) {
-				// streamed once per step (far beyond L2/MALL): non-temporal
-#if PINC_PUSH_CONSEC || !PINC_PUSH_NT
 				const dvec2 x = *reinterpret_cast<const dvec2 *>(a.xi[d] + i);
 				const dvec2 v = *reinterpret_cast<const dvec2 *>(a.vi[d] + i);
-#else
-				const dvec2 x = __builtin_nontemporal_load(reinterpret_cast<const dvec2 *>(a.xi[d] + i));
-				const dvec2 v = __builtin_nontemporal_load(reinterpret_cast<const dvec2 *>(a.vi[d] + i));
-#endif
 				p[k][d] = x.x;
 				p[k + 1][d] = x.y;
 				vv[k][d] = v.x;
@@ -2155,8 +1872,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 			}
 		}
 	}
-	// (negative: the loads at priority 0, the rest of the block at -PRIO)
-	if (PINC_PUSH_PRIO != 0) __builtin_amdgcn_s_setprio(PINC_PUSH_PRIO > 0 ? 0 : -PINC_PUSH_PRIO);
 	int cref[3] = {0, 0, 0};
 #pragma unroll
 	for (int d = 0; d < ND; d++) cref[d] = __builtin_amdgcn_readfirstlane((int)xref[d]);
@@ -2165,11 +1880,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	// own planes, so the slab dimension keeps its unmapped cells there (an
 	// image would move weight between ghost plane 0 and true plane T, which
 	// one fold treats alike and two do not)
-#ifndef PINC_LITERAL_SLAB_IMAGES
 	const int imgMask = a.g.literal ? (a.wrapMask & ~(1 << G.slab)) : a.wrapMask;
-#else
-	const int imgMask = a.wrapMask;  // (variant build: the round-4 mapping, for the regression test)
-#endif
 	const Images img = make_images(G, imgMask, cref, ND);
 	// cell range (and sum) of the block's items, in raw cells or in the
 	// images nearest the reference cell
@@ -2214,7 +1925,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		}
 		__syncthreads();
 	};
-#if PINC_PUSH_IMG_GATE
 	// The images differ from the raw cells only for a block whose items
 	// straddle a periodic boundary: with every raw cell within T/2 - 2 of the
 	// reference cell, the pre-move cells and the post-move cells of the
@@ -2234,10 +1944,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		          (cref[d] - x > G.T[d] / 2 - 2 || y - cref[d] > G.T[d] / 2 - 2);
 	}
 	if (useImg) cell_box(true);
-#else
-	const bool useImg = true;
-	cell_box(true);
-#endif
 	int clo[3] = {0, 0, 0}, chi[3] = {0, 0, 0}, cmid[3] = {0, 0, 0};
 #pragma unroll
 	for (int d = 0; d < ND; d++) {
@@ -2254,7 +1960,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	const Box eB = (KICK && !empty) ? make_box(clo, chi, cmid, 0, 1, ND, EC) : Box{{0, 0, 0}, {1, 1, 1}, 0};
 	const Box rB = !empty ? make_box(clo, chi, cmid, 1, 2, ND, RC) : Box{{0, 0, 0}, {1, 1, 1}, 0};
 	// (the sorting push's cell box: the core of its brick box ib below)
-	const int ahead = PINC_SORT_AHEAD ? 1 : 0;  // (sort cells: input cells +-1, sort_cell)
+	const int ahead = 1;  // (sort cells: input cells +-1, sort_cell)
 	const Box iB = (SORT && !empty) ? make_box(clo, chi, cmid, ahead, ahead, ND, kInCellCap) : Box{{0, 0, 0}, {1, 1, 1}, 0};
 	// the sorting push reserves per brick from the cursor of the brick's
 	// first cell, so the counting push counts per brick (at its first key):
@@ -2283,20 +1989,20 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 
 	PUSH_TS(1);
 	// ---- phase B: LDS setup (zero the accumulators, stage E)
-	// copies of the charge box (PINC_PUSH_COPIES): odd stride, so that the
+	// copies of the charge box (at most kPushCopies): odd stride, so that the
 	// copies of a node fall in different LDS banks
 	const int rStride = rB.vol | 1;
 	int nCopy = 1;
-	while (nCopy < PINC_PUSH_COPIES && 2 * nCopy * rStride <= RL) nCopy *= 2;
+	while (nCopy < kPushCopies && 2 * nCopy * rStride <= RL) nCopy *= 2;
 	const int myCopy = (lane & (nCopy - 1)) * rStride;
-	for (int t = threadIdx.x; t < (PINC_PUSH_COPIES ? nCopy * rStride : rB.vol); t += kPushThreads) rhoL[t] = 0.0;
+	for (int t = threadIdx.x; t < nCopy * rStride; t += kPushThreads) rhoL[t] = 0.0;
 	for (int t = threadIdx.x; t < (SORT ? kInCellCap : obb.vol); t += kPushThreads) cntOut[t] = 0;
 	// (cell ranking: block-uniform; bricks of at most 16 cells)
 	const int brickCellBits = a.tg.bs[0] + a.tg.bs[1] + a.tg.bs[2];
-	const bool cellRank = SORT && PINC_SORT_CELLRANK && ib.vol <= kCellRankBricks && brickCellBits <= 4;
+	const bool cellRank = SORT && ib.vol <= kCellRankBricks && brickCellBits <= 4;
 	if (cellRank)
 		for (int t = threadIdx.x; t < ib.vol * 16; t += kPushThreads) ccL[t] = 0;
-	if (KICK && !(PINC_PUSH_SKIP & 2)) {
+	if (KICK) {
 		const BoxRcp eq = box_rcp(eB);
 		for (int t = threadIdx.x; t < eB.vol; t += kPushThreads) {
 			int c[3] = {0, 0, 0};
@@ -2412,11 +2118,9 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	double ke = 0.0;
 	int cnt = 0, bad = 0;
 	unsigned dep = 0;
-#if PINC_PUSH_LEAN
 	bool thrInFrame = true;
 #pragma unroll
 	for (int d = 0; d < ND; d++) thrInFrame &= a.thr.lo[d] >= 0.0 && a.thr.up[d] <= a.thr.hi[d];
-#endif
 	// positions (and velocities if kicked or moved) of items k, k + 1
 	const bool wvel = KICK || a.vo[0] != a.vi[0];
 	auto store_pair = [&](int k) {
@@ -2425,14 +2129,8 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 #pragma unroll
 		for (int d = 0; d < ND; d++) {
 			if (ok1 && al) {
-#if PINC_PUSH_CONSEC || !PINC_PUSH_NT
 				*reinterpret_cast<dvec2 *>(a.xo[d] + i) = dvec2{p[k][d], p[k + 1][d]};
 				if (wvel) *reinterpret_cast<dvec2 *>(a.vo[d] + i) = dvec2{vv[k][d], vv[k + 1][d]};
-#else
-				__builtin_nontemporal_store(dvec2{p[k][d], p[k + 1][d]}, reinterpret_cast<dvec2 *>(a.xo[d] + i));
-				if (wvel)
-					__builtin_nontemporal_store(dvec2{vv[k][d], vv[k + 1][d]}, reinterpret_cast<dvec2 *>(a.vo[d] + i));
-#endif
 			} else {
 				if (ok0) a.xo[d][i] = p[k][d];
 				if (ok0 && wvel) a.vo[d][i] = vv[k][d];
@@ -2485,9 +2183,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 					return zc * (yc * (xc * f[0] + x * f[1]) + y * (xc * f[2] + x * f[3])) +
 					       z * (yc * (xc * f[4] + x * f[5]) + y * (xc * f[6] + x * f[7]));
 				};
-				if (PINC_PUSH_SKIP & 2) {
-					dv[0] = dv[1] = dv[2] = 0.0;
-				} else if (inE) {
+				if (inE) {
 					const int ei = eB.index(jc, ND);
 					double fx[NC], fy[NC];
 #pragma unroll
@@ -2525,12 +2221,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 				}
 			} else {
 				double e[NC][ND];
-				if (PINC_PUSH_SKIP & 2) {
-#pragma unroll
-					for (int c = 0; c < NC; c++)
-#pragma unroll
-						for (int q = 0; q < ND; q++) e[c][q] = 0.0;
-				} else if (inE) {
+				if (inE) {
 					const double *eb = eL + mul24(eB.index(jc, ND), ND);
 #pragma unroll
 					for (int c = 0; c < NC; c++)
@@ -2580,26 +2271,19 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		}
 		// drift + pVelAssertMax (population.c:342-365)
 		int chg = 0;
-#if PINC_PUSH_LEAN
 		int c0[3] = {0, 0, 0};  // pre-move cell (the statistic below)
 #pragma unroll
 		for (int d = 0; d < ND; d++) c0[d] = (int)p[k][d];
-#endif
 #pragma unroll
 		for (int d = 0; d < ND; d++) {
 			bad |= (vv[k][d] > a.maxVel);
 			p[k][d] += vv[k][d];
 			// cell changed (statistic for the sort schedule; recomputed, not kept)
-#if PINC_PUSH_LEAN
 			chg |= (int)p[k][d] != c0[d];
-#else
-			chg |= (int)p[k][d] != (int)(p[k][d] - vv[k][d]);
-#endif
 		}
 		// neighbour digit per dimension, as k_move_classify
 		int ne = 0;
 		bool outside = false;
-#if PINC_PUSH_LEAN
 		int digs[3] = {1, 1, 1};
 		bool leaves = false;
 #pragma unroll
@@ -2623,19 +2307,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		}
 #pragma unroll
 		for (int d = ND - 1; d >= 0; d--) ne = ne * 3 + digs[d];
-#else
-#pragma unroll
-		for (int d = ND - 1; d >= 0; d--) {
-			int dig = 1 - (p[k][d] < a.thr.lo[d]) + (p[k][d] >= a.thr.up[d]);
-			double q = p[k][d] - (double)(dig - 1) * (a.thr.hi[d] - 1.0);
-			outside |= (q < 0.0 || q > a.thr.hi[d]);
-			if ((a.wrapMask >> d) & 1) {
-				if (dig != 1) p[k][d] = p[k][d] + (double)((1 - dig) * a.thr.T[d]);
-				dig = 1;
-			}
-			ne = ne * 3 + dig;
-		}
-#endif
 		// pPosAssertInLocalFrame fails for this particle (the host stops the
 		// run with msg(ERROR) before the next deposit): route it to the
 		// emigrant path so that nothing indexes the grid with it
@@ -2673,35 +2344,14 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	// (all pairs after the last kick: storing each pair right after its
 	// kick, to free its velocity registers, measured 20.6 -> 26.2 ms per
 	// plain push at C4, profiles/r05j_push_early_store_ab.txt)
-#if PINC_PUSH_CONSEC && PINC_PUSH_XCH
-	if (!SORT && full && PINC_PUSH_XCH == 2) {
+	if (!SORT && full) {
 		// the load's row swap backwards (an involution)
 		const long q0 = base + wv * 256 + 2 * pi_lane((int)(threadIdx.x & 63));
 		auto put = [&](double *o, const double (*q)[ND], int d) {
 			dvec2 a0{q[0][d], q[1][d]}, a1{q[2][d], q[3][d]};
 			rowswap(a0, a1);
-			if (PINC_PUSH_XCH_NT & 2) {
-				__builtin_nontemporal_store(a0, reinterpret_cast<dvec2 *>(o + q0));
-				__builtin_nontemporal_store(a1, reinterpret_cast<dvec2 *>(o + q0 + 128));
-			} else {
-				*reinterpret_cast<dvec2 *>(o + q0) = a0;
-				*reinterpret_cast<dvec2 *>(o + q0 + 128) = a1;
-			}
-		};
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			put(a.xo[d], p, d);
-			if (wvel) put(a.vo[d], vv, d);
-		}
-	} else if (!SORT && full) {
-		// the load's exchange backwards: contiguous 16-B stores per wave
-		// instruction (pair lane, then pair 64 + lane)
-		const long q0 = base + wv * 256 + 2 * lane;
-		auto put = [&](double *o, const double (*q)[ND], int d) {
-			const dvec2 a0{q[0][d], q[1][d]}, a1{q[2][d], q[3][d]};
-			const dvec2 r = swap_adj(odd ? a0 : a1);
-			*reinterpret_cast<dvec2 *>(o + q0) = odd ? r : a0;
-			*reinterpret_cast<dvec2 *>(o + q0 + 128) = odd ? a1 : r;
+			__builtin_nontemporal_store(a0, reinterpret_cast<dvec2 *>(o + q0));
+			__builtin_nontemporal_store(a1, reinterpret_cast<dvec2 *>(o + q0 + 128));
 		};
 #pragma unroll
 		for (int d = 0; d < ND; d++) {
@@ -2709,7 +2359,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 			if (wvel) put(a.vo[d], vv, d);
 		}
 	} else
-#endif
 	if (!SORT) {
 #pragma unroll
 		for (int k = 0; k < kPushItems; k += 2) store_pair(k);
@@ -2744,7 +2393,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		}
 	}
 	PUSH_TS(5);
-	if (a.cntNext && PINC_PUSH_COUNT_RUNS) {
+	if (a.cntNext) {
 		// count the output bricks of the particles that stay (next push's
 		// sort): a thread's consecutive items mostly share one, so the items in
 		// the brick of its first counted item add once (plain LDS atomics)
@@ -2762,21 +2411,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 			if (mine && lb < 0) atomicAdd(&a.cntNext[brick_first_key<ND>(a.tg, c)], 1);
 		}
 		if (nm) atomicAdd(&cntOut[l0], nm);
-	} else if (a.cntNext) {
-		// count the output bricks of the particles that stay (next push's sort)
-#pragma unroll
-		for (int k = 0; k < kPushItems; k++) {
-			const bool mine = (dep >> k) & 1u;
-			int c[3] = {0, 0, 0};
-#pragma unroll
-			for (int d = 0; d < ND; d++) c[d] = sort_cell(p[k][d], vv[k][d]);
-			const int lb = mine ? brick_inside<ND>(a.tg, obb, c) : -1;
-			// (aggregated: plain atomics here, or after the deposit, cost the
-			// plain instance, which carries this code behind a runtime test,
-			// 48-52 spilled VGPRs; aggregated after the deposit: same time)
-			lds_agg_add<false>(cntOut, lb < 0 ? 0 : lb, lb >= 0);
-			if (mine && lb < 0) atomicAdd(&a.cntNext[brick_first_key<ND>(a.tg, c)], 1);
-		}
 	}
 	if (bad) atomicOr(a.err, bad);
 	if (!SORT || a.emigTotal) {
@@ -2825,7 +2459,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	};
 	auto add8 = [&](const int *j, int l0, const double *w) {
 		if (l0 >= 0) {
-			if (PINC_PUSH_COPIES) l0 += myCopy;
+			l0 += myCopy;
 #pragma unroll
 			for (int c = 0; c < NC; c++) atomicAdd(&rhoL[l0 + coff[c]], w[c]);
 		} else {
@@ -2860,46 +2494,6 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		}
 		return kk;
 	};
-	// one wave pass: lanes sharing a cell (up to kPushGroups groups of at
-	// least kPushGroupMin lanes) are summed across the wave and added once,
-	// the others add their weights one by one
-	auto deposit_pass = [&](bool mine, const int *j, const double *w, int key, int l0) {
-		unsigned long long pend = __ballot(mine);
-		unsigned long long indiv = 0;
-#pragma unroll 1
-		for (int grp = 0; grp < kPushGroups && pend; grp++) {
-			int leader = (grp & 1) ? 63 - __clzll((long long)pend) : __ffsll((long long)pend) - 1;
-			int lk = __shfl(key, leader, 64);
-			unsigned long long m = __ballot(key == lk) & pend;
-			pend &= ~m;
-			if (__popcll(m) < kPushGroupMin) {
-				indiv |= m;
-				continue;
-			}
-			double r[8];
-			const bool in = (m >> lane) & 1ull;
-#pragma unroll
-			for (int c = 0; c < 8; c++) r[c] = in ? w[c] : 0.0;
-			double sum = wave_reduce8(r);
-			const int corner = lane >> 3;
-			const int ll = __shfl(l0, leader, 64);  // leader's box cell (every lane active)
-			if (ll >= 0) {
-				if ((lane & 7) == 0 && corner < NC) atomicAdd(&rhoL[ll + coff[corner]], sum);
-			} else {
-				int jl[3] = {0, 0, 0};
-#pragma unroll
-				for (int d = 0; d < ND; d++) jl[d] = __shfl(j[d], leader, 64);
-				if ((lane & 7) == 0 && corner < NC) add_corner_global(jl, corner, sum);
-			}
-		}
-		indiv |= pend;
-		if ((indiv >> lane) & 1ull) add8(j, l0, w);
-	};
-	// the two particles of a lane's pair are neighbours in memory and mostly
-	// share a cell: their weights are summed in the lane first, so one wave
-	// pass covers the pair's 128 particles; the second particle of a pair
-	// that straddles a cell adds its weights one by one
-#if PINC_PUSH_CONSEC && PINC_PUSH_COPIES
 	// consecutive particles of the thread: runs of one cell are summed in
 	// registers and added once (8 LDS atomics per run)
 	{
@@ -2907,7 +2501,7 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		double wr[8];
 		bool open = false;
 #pragma unroll
-		for (int k = 0; k < ((PINC_PUSH_SKIP & 1) ? 0 : kPushItems); k++) {
+		for (int k = 0; k < kPushItems; k++) {
 			if (!((dep >> k) & 1u)) continue;
 			int jk[3] = {0, 0, 0};
 			double wk[8];
@@ -2927,57 +2521,19 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 		}
 		if (open) add8(jr, box_cell(jr), wr);
 	}
-	if (false)
-#endif
-#pragma unroll
-	for (int k = 0; k < ((PINC_PUSH_SKIP & 1) ? 0 : kPushItems); k += 2) {
-		const bool m0 = (dep >> k) & 1u, m1 = (dep >> (k + 1)) & 1u;
-		int j[3] = {0, 0, 0}, j1[3] = {0, 0, 0};
-		double w[8], w1[8];
-#pragma unroll
-		for (int c = 0; c < 8; c++) w[c] = w1[c] = 0.0;
-		int key = -1, key1 = -2;
-		if (m0) key = weights(k, j, w);
-		if (m1) key1 = weights(k + 1, j1, w1);
-		const bool merge = m0 && m1 && key == key1;
-		if (merge) {
-#pragma unroll
-			for (int c = 0; c < 8; c++) w[c] += w1[c];
-		} else if (!m0 && m1) {
-#pragma unroll
-			for (int d = 0; d < 3; d++) j[d] = j1[d];
-#pragma unroll
-			for (int c = 0; c < 8; c++) w[c] = w1[c];
-			key = key1;
-		}
-		const int l0 = (m0 || m1) ? box_cell(j) : -1;
-		if (PINC_PUSH_COPIES) {
-			if (m0 || m1) add8(j, l0, w);
-		} else {
-			deposit_pass(m0 || m1, j, w, key, l0);
-		}
-		if (m0 && m1 && !merge) add8(j1, box_cell(j1), w1);
-	}
 
 	if (KICK) {
-#if PINC_DPP_REDUCE
 		// per-wave sums with DPP (no LDS shuffles); the block barrier below
 		// publishes them
 		const double w = wave_sum_d(ke);
 		if (lane == 0) kered[wv] = w;
-#else
-		double t = block_sum(ke, kered);
-		if (threadIdx.x == 0) a.kePartial[chunk] = t;
-#endif
 	}
 	__syncthreads();
-#if PINC_DPP_REDUCE
 	if (KICK && threadIdx.x == 0) {
 		double t = 0.0;
 		for (int w = 0; w < NW; w++) t += kered[w];
 		a.kePartial[chunk] = t;
 	}
-#endif
 	if ((!SORT || a.emigTotal) && threadIdx.x == 0) {
 		int t = 0;
 		for (int w = 0; w < NW; w++) t += wcnt[w];
@@ -2997,10 +2553,9 @@ __global__ __launch_bounds__(kPushThreads) __attribute__((amdgpu_waves_per_eu(PI
 	}
 	// flush: one global atomic per touched node / output cell
 	const BoxRcp rq = box_rcp(rB);
-	for (int t = threadIdx.x; t < ((PINC_PUSH_SKIP & 4) ? 0 : rB.vol); t += kPushThreads) {
+	for (int t = threadIdx.x; t < rB.vol; t += kPushThreads) {
 		double v = rhoL[t];
-		if (PINC_PUSH_COPIES)
-			for (int c = 1; c < nCopy; c++) v += rhoL[c * rStride + t];
+		for (int c = 1; c < nCopy; c++) v += rhoL[c * rStride + t];
 		if (v == 0.0) continue;
 		int c[3] = {0, 0, 0};
 		box_coords(rB, rq, t, c, ND);
@@ -3430,7 +2985,7 @@ extern "C" int pinc_hip_init_species(pinc_pop_t pop, int s, pinc_geom_t g, long 
 	return check_launch("init_species");
 }
 
-// PINC_SORT_BRICK: the sorting push reserves its output per brick of
+// The sorting push reserves its output per brick of
 // tw^(nd-1) cells (tw x tw x 1 in 3-D, one block's worth at C4's 64 ppc)
 // instead of per cell: a few tens of runs per block instead of about a
 // hundred short scattered ones once the input order has decayed; inside a
@@ -3438,9 +2993,6 @@ extern "C" int pinc_hip_init_species(pinc_pop_t pop, int s, pinc_geom_t g, long 
 // ordered along the slab dimension fastest, so that consecutive bricks are
 // neighbours -- the plain pushes got slower, 25 -> 31 ms per ion launch at
 // C4: the concurrently running blocks then touch scattered grid rows.)
-#ifndef PINC_SORT_BRICK
-#define PINC_SORT_BRICK 1
-#endif
 
 static TileGeo make_tile_geo(pinc_geom_t g, int tileWidth, long *nKeys) {
 	TileGeo tg;
@@ -3448,7 +3000,7 @@ static TileGeo make_tile_geo(pinc_geom_t g, int tileWidth, long *nKeys) {
 	tg.tw = tileWidth;
 	int lw = 0;
 	while ((1 << lw) < tileWidth) lw++;
-	const bool brick = PINC_SORT_BRICK && (1 << lw) == tileWidth;
+	const bool brick = (1 << lw) == tileWidth;
 	for (int d = 0; d < 3; d++) {
 		int T = d < g.nd ? (d == g.nd - 1 ? g.nloc : g.T[d]) : 1;
 		tg.cmax[d] = T + 1;

@@ -64,7 +64,7 @@ def test_fused_sweep_equals_two_passes(hip, shape):
 
 @pytest.mark.parametrize("shape", [(32, 8, 16), (64, 32, 96), (32, 16, 64), (96, 24, 32)])
 def test_double_sweep_equals_two_sweeps(hip, shape):
-    """k_gs_sweep4 (two red-black iterations per launch, four-stage z-march)
+    """k_gs_sweep4c (two red-black iterations per launch, four-stage z-march)
     is bit for bit equal to two single-iteration sweeps, and to the numpy
     restatement of two red-black iterations."""
     import torch

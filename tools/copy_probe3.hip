@@ -3,7 +3,7 @@
 //
 // The measured copy ceiling (tools/copy_probe2.hip, "push": 6.09-6.35 TB/s)
 // maps a wave instruction to 1 KB of contiguous 16-B vectors.  k_push
-// (PINC_PUSH_CONSEC) gives each thread four consecutive particles: its two
+// gives each thread four consecutive particles: its two
 // 16-B loads per array sit 16 B apart, so one wave instruction covers every
 // other 16 B of 2 KB and the next instruction the rest.  Variants, 6 arrays
 // of the C4 species size (3 positions to other arrays, 3 velocities in

@@ -9,7 +9,7 @@
 //   rd_b32 / rd_b64 / rd_b128  consecutive 4 / 8 / 16 B per lane
 //   rd_pair32                  k_push's particle loads: lane l reads 16 B at
 //                              32 l and, in a second instruction, 16 B at
-//                              32 l + 16 (PINC_PUSH_CONSEC)
+//                              32 l + 16 (a thread's own four consecutive particles)
 //   rd_b64_rows                k_mg's stencil loads: 8 B per lane, each
 //                              thread reads its row and the rows +-1 (a
 //                              3-row sliding window: every byte is fetched
