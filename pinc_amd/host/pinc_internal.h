@@ -251,17 +251,17 @@ struct MultigridSolver {
 	long N[PINC_MAX_LEVELS];
 	double *rho[PINC_MAX_LEVELS], *phi[PINC_MAX_LEVELS], *res[PINC_MAX_LEVELS];
 	/* native smoothing ping-pongs phi[q] and res[q] by swapping the
-	 * pointers; swapped[q] = 1 while they are exchanged (pp_restore) */
+	 * pointers (pp_swap); swapped[q] = 1 while they are exchanged (pp_restore) */
 	int swapped[PINC_MAX_LEVELS];
 	long cycles;
-	Grid *rhoGrid, *phiGrid;
-	int native;
-	int useGraph;      /* multigrid:graph: replay one captured V-cycle */
+	Grid *phiGrid;     /* its extended-slab pointer is cleared when the solver goes */
+	int native, useGraph; /* multigrid:native; multigrid:graph: replay one captured V-cycle */
 	void *cycleGraph;  /* instantiated graph of vrec(S, 0) */
 	/* diagnostics: RMS residual after each V-cycle of the last solve, and an
-	 * optional cap on the cycles of one solve (0 = loop until converged) */
+	 * optional cap on the cycles of one solve (0 = loop until converged):
+	 * maxCycles (mgSetLimit, a diagnostic run to pinc_mg_stop), else envCap */
 	double *hist;
-	long histCap, histN, maxCycles;
+	long histCap, histN, maxCycles, envCap; /* envCap: PINC_MG_MAX_CYCLES */
 	long fusedMin;     /* smallest level (points) smoothed by the fused sweeps */
 	/* multigrid:extrapolate: level-0 initial guesses (pinc_mg.c guess_*).
 	 * Runs without objects: 2 phi_n - phi_{n-1} (phiPrev holds phi_{n-1};
@@ -321,6 +321,14 @@ struct MultigridSolver {
 	double *smallOut, *hostSmall;
 	double *smallBasis; /* with multigrid:spectralCoarse: level 1's Fourier basis and eigenvalues */
 };
+
+/* the multigrid driver's decisions as pure functions (pinc_mg.c; exported
+ * for the CPU tests, not part of include/pinc.h) */
+enum { PINC_MG_PASSES = 0, PINC_MG_SINGLE = 1, PINC_MG_DOUBLE = 2 };
+enum { PINC_MG_CONTINUE = 0, PINC_MG_CONVERGED, PINC_MG_STOP_CAP, PINC_MG_STOP_NONFINITE, PINC_MG_ERROR };
+int pinc_mg_smooth_form(pinc_lvl_t L, long n, int nd3, int shard0, long fusedMin, int aligned);
+int pinc_mg_smooth_next(int form, int shard0, int left, int *iters);
+int pinc_mg_stop(double barRes, long cycles, long cap, int diagnostic);
 
 /* gFinDiff1st and gMul(field, -1) in one pass, bit for bit the two
  * (pinc_grid.c; regular()'s step) */

@@ -11,10 +11,11 @@
  *   smoothers          mgGS3D / mgGSND red-black Gauss-Seidel with a
  *                      neutralisation after every colour (gBnd -> grid.c:730)
  * Coarse-level potentials persist between cycles and steps (warm start) as in
- * the reference.  The solve runs on the whole periodic domain on every rank:
- * with several ranks the slabs of rho are all-gathered first (RCCL) and every
- * rank computes the same potential, replacing the reference's per-colour
- * halo exchanges (DESIGN.md "Multi-GPU").
+ * the reference; native mode is the correction scheme.
+ *   replicated solve    every rank solves the all-gathered global grid (section 6)
+ *   sharded level 0     native: each rank smooths its z-slab with a deep halo (section 7)
+ *   decomposed level 1  sharded with multigrid:spectralCoarse: slab transform (section 7)
+ *   one-workgroup solve native, small 2-D grids: one launch per solve (section 6)
  */
 #define _GNU_SOURCE
 #include "pinc_internal.h"
@@ -154,13 +155,32 @@ static void small_basis(MultigridSolver *S, int n) {
 	free(h);
 }
 
+/* The stop rule of every solve: converged at an RMS
+ * residual <= 1e-10; one that is not finite ends the solve at once, an error
+ * unless a diagnostic run (mgSetLimit) wants the history; then the cap; the
+ * reference's unbounded loop (multigrid.c:1698) gives up after 10^6 cycles */
+int pinc_mg_stop(double barRes, long cycles, long cap, int diagnostic) {
+	if (!isfinite(barRes)) return diagnostic ? PINC_MG_STOP_NONFINITE : PINC_MG_ERROR;
+	if (barRes <= 1.E-10) return PINC_MG_CONVERGED;
+	if (cap > 0 && cycles >= cap) return PINC_MG_STOP_CAP;
+	return cycles > 1000000 ? PINC_MG_ERROR : PINC_MG_CONTINUE;
+}
+
+static void report_stop(int stop, double barRes, long c) {
+	if (stop == PINC_MG_ERROR) msg(ERROR, "multigrid did not converge (residual %g)", barRes);
+	if (stop == PINC_MG_STOP_NONFINITE)
+		fprintf(stderr, "[pinc] rank %d solve stopped: residual %g after %ld cycles\n", g_pinc.rank, barRes, c);
+	if (stop == PINC_MG_STOP_CAP)
+		fprintf(stderr, "[pinc] rank %d solve stopped at the PINC_MG_MAX_CYCLES cap (%ld), residual %.3e\n",
+		        g_pinc.rank, c, barRes);
+}
+
 /* the V-cycles of one solve in launches of at most kSmallChunk cycles (at
- * most kSmallHist when a history is kept), until the RMS residual is at most
- * 1e-10 as mgSolve's loop; returns the cycles run */
-static long small_solve(MultigridSolver *S, long cap, double *lastRes) {
+ * most kSmallHist when a history is kept), until pinc_mg_stop ends it */
+static int small_solve(MultigridSolver *S, long cap, long *cycles, double *barRes) {
 	long c = 0;
-	double barRes = 2.;
-	for (;;) {
+	int stop;
+	do {
 		long chunk = S->histCap > 0 ? kSmallHist : kSmallChunk;
 		if (cap > 0 && cap - c < chunk) chunk = cap - c;
 		int slot = pinc_probe_begin(PINC_PROBE_CYCLE);
@@ -170,7 +190,7 @@ static long small_solve(MultigridSolver *S, long cap, double *lastRes) {
 		pinc_probe_end(PINC_PROBE_CYCLE, slot, 0.0);
 		pinc_check(pinc_hip_d2h(S->hostSmall, S->smallOut, kSmallOut * sizeof(double), g_pinc.stream), "mg small solve");
 		const long n = (long)S->hostSmall[0];
-		barRes = S->hostSmall[1];
+		*barRes = S->hostSmall[1];
 		for (long k = 0; k < n; k++) {
 			if (S->histN < S->histCap) S->hist[S->histN] = k < kSmallHist ? S->hostSmall[2 + k] : NAN;
 			S->histN++;
@@ -182,11 +202,10 @@ static long small_solve(MultigridSolver *S, long cap, double *lastRes) {
 		}
 		c += n;
 		S->cycles += n;
-		if (!(barRes > 1.E-10) || !isfinite(barRes) || (cap > 0 && c >= cap)) break;
-		if (c > 1000000) break;
-	}
-	*lastRes = barRes;
-	return c;
+		stop = pinc_mg_stop(*barRes, c, cap, S->maxCycles != 0);
+	} while (stop == PINC_MG_CONTINUE);
+	*cycles = c;
+	return stop;
 }
 
 MultigridSolver *mgAllocSolver(const dictionary *ini, Grid *rho, Grid *phi) {
@@ -236,6 +255,8 @@ MultigridSolver *mgAllocSolver(const dictionary *ini, Grid *rho, Grid *phi) {
 	 * z-marching fused sweeps (two iterations per launch), smaller ones
 	 * colour by colour (PINC_MG_FUSED_MIN overrides, experiments) */
 	S->fusedMin = getenv("PINC_MG_FUSED_MIN") ? atol(getenv("PINC_MG_FUSED_MIN")) : (1L << 23);
+	/* PINC_MG_MAX_CYCLES caps every solve for diagnostics (stops with a warning) */
+	S->envCap = getenv("PINC_MG_MAX_CYCLES") ? atol(getenv("PINC_MG_MAX_CYCLES")) : 0;
 	for (int d = 1; d <= nd; d++)
 		if (rho->trueSize[d] % (1 << S->nLevels))
 			msg(ERROR, "All elements in grid:trueSize must be a multiple of 2^mgLevels=%d", 1 << S->nLevels);
@@ -367,7 +388,6 @@ MultigridSolver *mgAllocSolver(const dictionary *ini, Grid *rho, Grid *phi) {
 		pinc_check(pinc_hip_malloc((void **)&S->phiB, S->N[0] * sizeof(double)), "mg extrapolation");
 		pinc_check(pinc_hip_malloc((void **)&S->dCorr, S->N[0] * sizeof(double)), "mg extrapolation");
 	}
-	S->rhoGrid = rho;
 	S->phiGrid = phi;
 	return S;
 }
@@ -560,99 +580,99 @@ static void restrict_residual(MultigridSolver *S, int q) {
 	if (S->native) pinc_check(pinc_hip_scale(S->rho[q + 1], S->N[q + 1], 4.0, g_pinc.stream), "native scale");
 }
 
-/* nIter red-black iterations, each colour followed by a neutralisation:
- * the mean of pass k is formed from that pass's partial sums and applied
- * lazily by pass k+1 (k_mg.hip), then materialised once at the end. */
-/* native mode: red-black iterations without the per-colour neutralisation;
- * full sweeps in one pass where the level tiles (pinc_hip_gs_sweep, ping-pong
- * through res[q], which is free while smoothing), an odd last one in place */
-static void smooth_native(MultigridSolver *S, int q, int nIter, int nd3) {
-	const pinc_lvl_t L = S->L[q];
-	/* the z-marching fused sweep pays off on large levels only (measured at
-	 * 256^3: 128^3 and below are as fast, launch-latency bound, as two
-	 * passes; rechecked with the 32x8 two-ahead sweep) */
-	int fused = nd3 && L.nd == 3 && L.T[0] % 16 == 0 && L.T[1] % 16 == 0 && L.T[2] % 16 == 0 &&
-	            (S->N[q] >= S->fusedMin || (q == 0 && S->shard && S->N[q] >= S->fusedMin / 4));
-	int k = 0;
-	/* two iterations per launch (pinc_hip_gs_sweep2x) in pairs, so that the
-	 * ping-pong ends in phi */
-	/* (its x-pair fetches need 16-B aligned arrays: otherwise the single
-	 * sweeps, as the residual norm and the restriction fall back to their
-	 * scalar kernels -- every x-pair kernel falls back, none fails) */
-	int fused2 = fused && L.T[0] % 32 == 0 && L.T[1] % 8 == 0 &&
-	             !(((uintptr_t)S->phi[q] | (uintptr_t)S->res[q] | (uintptr_t)S->rho[q]) & 15);
-	if (q == 0 && S->preDone) {
-		/* the first double sweep ran while the host read the last cycle's
-		 * norm (mgSolve), and its ping-pong swap is applied */
-		if (!(fused2 && !S->shard && nIter >= 2)) msg(ERROR, "mg: a speculative sweep the smoothing cannot use");
-		S->preDone = 0;
-		k = 2;
-	}
-	if (fused2 && !(q == 0 && S->shard)) {
-		/* one launch per two iterations, phi[q] -> res[q], then the pointers
-		 * swap (round 4: a smoothing of 10 is five double sweeps instead of
-		 * four and a pair of single ones; the V-cycle's other kernels take
-		 * whichever buffer holds the iterate, pp_restore puts it back) */
-		for (; k + 2 <= nIter; k += 2) {
-			int slot = q == 0 && (k & 2) == 0 ? pinc_probe_begin(PINC_PROBE_GS) : -1;
-			if (q == 0 && (k & 2)) pinc_probe_count(PINC_PROBE_GS);
-			pinc_check(pinc_hip_gs_sweep2x(S->phi[q], S->res[q], S->rho[q], L, g_pinc.stream), "gs sweep2x");
-			pinc_probe_end(PINC_PROBE_GS, slot, 24.0 * S->N[q]);
-			double *t = S->phi[q];
-			S->phi[q] = S->res[q];
-			S->res[q] = t;
-			S->swapped[q] ^= 1;
-		}
-	}
-	if (fused2 && q == 0 && S->shard) {
-		for (; k + 4 <= nIter; k += 4) {
-			int slot = q == 0 ? pinc_probe_begin(PINC_PROBE_GS) : -1;
-			pinc_check(pinc_hip_gs_sweep2x(S->phi[q], S->res[q], S->rho[q], L, g_pinc.stream), "gs sweep2x");
-			/* two full iterations: phi R + W, rho R (24 B per point) once */
-			pinc_probe_end(PINC_PROBE_GS, slot, 24.0 * S->N[q]);
-			pinc_probe_count(PINC_PROBE_GS);
-			pinc_check(pinc_hip_gs_sweep2x(S->res[q], S->phi[q], S->rho[q], L, g_pinc.stream), "gs sweep2x");
-		}
-	}
-	if (fused) {
-		for (; k + 2 <= nIter; k += 2) {
-			int slot = q == 0 && !fused2 ? pinc_probe_begin(PINC_PROBE_GS) : -1;
-			pinc_check(pinc_hip_gs_sweep(S->phi[q], S->res[q], S->rho[q], L, g_pinc.stream), "gs sweep");
-			/* one full iteration: phi R + W, rho R (24 B per point) */
-			pinc_probe_end(PINC_PROBE_GS, slot, 24.0 * S->N[q]);
-			if (q == 0 && !fused2) pinc_probe_count(PINC_PROBE_GS);
-			pinc_check(pinc_hip_gs_sweep(S->res[q], S->phi[q], S->rho[q], L, g_pinc.stream), "gs sweep");
-		}
-	}
-	for (; k < nIter; k++) {
-		for (int pass = 0; pass < 2; pass++) {
-			int nb = 0;
-			pinc_check(pinc_hip_gs_pass(S->phi[q], S->rho[q], L, pass, nd3, NULL, NULL, &nb, g_pinc.stream),
-			           "gs pass");
-		}
-	}
+/* Which smoother a native level gets.  The z-marching fused sweeps need
+ * extents in 16s and pay off on large levels only (measured at 256^3: 128^3
+ * and below are as fast, launch-latency bound, as two colour passes; the
+ * sharded level 0 from fusedMin / 4).  Two iterations per launch need the
+ * 32x8 tile and, for their x-pair fetches, 16-B aligned phi|res|rho (every
+ * x-pair kernel falls back to its scalar form, none fails). */
+int pinc_mg_smooth_form(pinc_lvl_t L, long n, int nd3, int shard0, long fusedMin, int aligned) {
+	if (!(nd3 && L.nd == 3 && L.T[0] % 16 == 0 && L.T[1] % 16 == 0 && L.T[2] % 16 == 0)) return PINC_MG_PASSES;
+	if (!(n >= fusedMin || (shard0 && n >= fusedMin / 4))) return PINC_MG_PASSES;
+	return L.T[0] % 32 == 0 && L.T[1] % 8 == 0 && aligned ? PINC_MG_DOUBLE : PINC_MG_SINGLE;
 }
 
-/* level 0's pre-smoothing opens with one pinc_hip_gs_sweep2x phi -> res
- * (smooth_native's fused2 branch): the sweep mgSolve may queue ahead */
-static int first_sweep_is_double(const MultigridSolver *S) {
-	const pinc_lvl_t L = S->L[0];
-	if (!S->native || S->shard || S->nPre < 2 || !S->pre3d) return 0;
-	int fused = L.nd == 3 && L.T[0] % 16 == 0 && L.T[1] % 16 == 0 && L.T[2] % 16 == 0 && S->N[0] >= S->fusedMin;
-	return fused && L.T[0] % 32 == 0 && L.T[1] % 8 == 0 &&
-	       !(((uintptr_t)S->phi[0] | (uintptr_t)S->res[0] | (uintptr_t)S->rho[0]) & 15);
+/* The next step of a smoothing with `left` iterations to go: a double sweep
+ * phi -> res (replicated: then the pointers swap, 2 iterations; sharded level
+ * 0: then one back, 4), a single sweep there and back (2), or a red and a
+ * black colour pass in place (1); the iterate always ends where phi[q] points */
+int pinc_mg_smooth_next(int form, int shard0, int left, int *iters) {
+	int kind = PINC_MG_PASSES;
+	if (form == PINC_MG_DOUBLE && left >= (shard0 ? 4 : 2)) kind = PINC_MG_DOUBLE;
+	else if (form != PINC_MG_PASSES && left >= 2) kind = PINC_MG_SINGLE;
+	*iters = kind == PINC_MG_PASSES ? 1 : kind == PINC_MG_DOUBLE && shard0 ? 4 : 2;
+	return kind;
+}
+
+static int level_form(const MultigridSolver *S, int q, int nd3) {
+	const int aligned = !(((uintptr_t)S->phi[q] | (uintptr_t)S->res[q] | (uintptr_t)S->rho[q]) & 15);
+	return pinc_mg_smooth_form(S->L[q], S->N[q], nd3, q == 0 && S->shard, S->fusedMin, aligned);
+}
+
+/* ping-pong: the iterate is in res[q], which phi[q] names from now on */
+static void pp_swap(MultigridSolver *S, int q) {
+	double *t = S->phi[q];
+	S->phi[q] = S->res[q];
+	S->res[q] = t;
+	S->swapped[q] ^= 1;
 }
 
 /* the iterate back into phi[q]'s own buffer after a swapped smoothing */
 static void pp_restore(MultigridSolver *S, int q) {
 	if (!S->swapped[q]) return;
 	pinc_check(pinc_hip_d2d(S->res[q], S->phi[q], S->N[q] * sizeof(double), g_pinc.stream), "mg ping-pong");
-	double *t = S->phi[q];
-	S->phi[q] = S->res[q];
-	S->res[q] = t;
-	S->swapped[q] = 0;
+	pp_swap(S, q);
 }
 
+static void sweep(MultigridSolver *S, int q, int dbl, const double *src, double *dst) {
+	if (dbl) pinc_check(pinc_hip_gs_sweep2x(src, dst, S->rho[q], S->L[q], g_pinc.stream), "gs sweep2x");
+	else pinc_check(pinc_hip_gs_sweep(src, dst, S->rho[q], S->L[q], g_pinc.stream), "gs sweep");
+}
+
+/* native mode: red-black iterations without the per-colour neutralisation,
+ * in the steps of pinc_mg_smooth_next (res[q] is free while smoothing) */
+static void smooth_native(MultigridSolver *S, int q, int nIter, int nd3) {
+	const int shard0 = q == 0 && S->shard, form = level_form(S, q, nd3);
+	int k = 0, iters;
+	if (q == 0 && S->preDone) {
+		/* the first double sweep ran while the host read the last norm (residual_norm); its swap is applied */
+		if (form != PINC_MG_DOUBLE || shard0 || nIter < 2) msg(ERROR, "mg: a speculative sweep the smoothing cannot use");
+		S->preDone = 0;
+		k = 2;
+	}
+	for (; k < nIter; k += iters) {
+		const int kind = pinc_mg_smooth_next(form, shard0, nIter - k, &iters);
+		if (kind == PINC_MG_PASSES) {
+			for (int pass = 0, nb = 0; pass < 2; pass++)
+				pinc_check(pinc_hip_gs_pass(S->phi[q], S->rho[q], S->L[q], pass, nd3, NULL, NULL, &nb, g_pinc.stream),
+				           "gs pass");
+			continue;
+		}
+		/* level 0's probe: of each two launches the first is timed (phi R + W,
+		 * rho R: 24 B per point), the second counted; the single sweeps left
+		 * over by a double-sweep schedule are neither */
+		const int dbl = kind == PINC_MG_DOUBLE, back = shard0 || !dbl;
+		const int probed = q == 0 && (dbl || form != PINC_MG_DOUBLE), timed = probed && (back || !(k & 2));
+		int slot = timed ? pinc_probe_begin(PINC_PROBE_GS) : -1;
+		if (probed && !timed) pinc_probe_count(PINC_PROBE_GS);
+		sweep(S, q, dbl, S->phi[q], S->res[q]);
+		pinc_probe_end(PINC_PROBE_GS, slot, 24.0 * S->N[q]);
+		if (back) {
+			if (probed) pinc_probe_count(PINC_PROBE_GS);
+			sweep(S, q, dbl, S->res[q], S->phi[q]);
+		} else pp_swap(S, q);
+	}
+}
+
+/* level 0's pre-smoothing opens with the double sweep phi -> res that residual_norm may queue ahead */
+static int first_sweep_is_double(const MultigridSolver *S) {
+	return S->native && !S->shard && S->nPre >= 2 && level_form(S, 0, S->pre3d) == PINC_MG_DOUBLE;
+}
+
+/* parity mode: nIter red-black iterations, each colour followed by a
+ * neutralisation: the mean of pass k is formed from that pass's partial sums
+ * and applied lazily by pass k+1 (k_mg.hip), then materialised once at the
+ * end.  (Native mode, the sharded level 0 in chunks: smooth_native.) */
 static void smooth(MultigridSolver *S, int q, int nIter, int nd3) {
 	if (nIter <= 0) return;
 	if (q == 0 && S->shard) {
@@ -761,12 +781,9 @@ static void vrec(MultigridSolver *S, int q) {
 	if (q > 0) prolong_into(S, q - 1);
 }
 
-void mgSolve(MultigridSolver *S, Grid *rho, Grid *phi, const MpiInfo *mpiInfo) {
-	(void)mpiInfo;
-	(void)phi;
-	pinc_phase_begin(4);
+/* rho into level 0: this rank's slab with the neighbours' halo (sharded), or all slabs on every rank */
+static void gather_rho(MultigridSolver *S, const Grid *rho) {
 	if (S->shard) {
-		/* this rank's rho into the extended slab, halo from the neighbours */
 		long ps = S->ps0;
 		pinc_check(pinc_hip_d2d(S->rho[0] + (long)S->hz * ps, rho->dev->d + ps, ps * S->nloc0 * sizeof(double),
 		                        g_pinc.stream),
@@ -776,114 +793,107 @@ void mgSolve(MultigridSolver *S, Grid *rho, Grid *phi, const MpiInfo *mpiInfo) {
 		long ps = rho->dev->planeSize;
 		pinc_comm_allgather(rho->dev->d + ps, rho->dev->global, ps * rho->dev->geom.nloc, "gather rho");
 	}
+}
+
+/* one V-cycle; with multigrid:graph it is a fixed launch sequence on fixed
+ * buffers, captured once, then replayed (no per-kernel dispatch) */
+static void run_cycle(MultigridSolver *S) {
+	if (!S->useGraph) vrec(S, 0);
+	else {
+		if (!S->cycleGraph) {
+			g_pinc.capturing = 1;
+			pinc_check(pinc_hip_capture_begin(g_pinc.stream), "capture V-cycle");
+			vrec(S, 0);
+			pinc_check(pinc_hip_capture_end(g_pinc.stream, &S->cycleGraph), "capture V-cycle");
+			g_pinc.capturing = 0;
+		}
+		int gslot = pinc_probe_begin(PINC_PROBE_CYCLE);
+		pinc_check(pinc_hip_graph_launch(S->cycleGraph, g_pinc.stream), "V-cycle graph");
+		pinc_probe_end(PINC_PROBE_CYCLE, gslot, 0.0);
+	}
+	S->cycles++;
+}
+
+/* RMS residual of level 0.  When speculating, the norm goes to pinned memory
+ * and, while the host waits for it, the next cycle's first double sweep (phi
+ * -> res: phi untouched) is queued if another cycle is expected and would open
+ * with it; the caller applies the swap if that cycle is run (*queued). */
+static double residual_norm(MultigridSolver *S, int moreExpected, int *queued) {
+	int nb = 0, slot = pinc_probe_begin(PINC_PROBE_RESIDUAL);
+	if (S->shard) {
+		/* owned planes, summed over the ranks */
+		pinc_check(pinc_hip_residual_sumsq_slab(S->phi[0], S->rho[0], S->L[0], S->hz, S->hz + S->nloc0, g_pinc.dScratch,
+		                                        &nb, g_pinc.stream),
+		           "residual norm");
+		pinc_probe_end(PINC_PROBE_RESIDUAL, slot, 16.0 * S->ps0 * S->nloc0);
+	} else {
+		pinc_check(pinc_hip_residual_sumsq(S->phi[0], S->rho[0], S->L[0], g_pinc.dScratch, &nb, g_pinc.stream),
+		           "residual norm");
+		pinc_probe_end(PINC_PROBE_RESIDUAL, slot, 16.0 * S->N[0]);
+	}
+	pinc_check(pinc_hip_reduce(g_pinc.dScratch, nb, 1.0, PINC_SLOT(TMP_SLOT + 1), g_pinc.stream), "norm");
+	if (S->shard && g_pinc.nranks > 1) pinc_comm_allreduce_sum(PINC_SLOT(TMP_SLOT + 1), 1, "norm");
+	*queued = S->speculate && moreExpected && !S->swapped[0] && first_sweep_is_double(S);
+	if (S->speculate) {
+		pinc_check(pinc_hip_d2h_async(S->hostNorm, PINC_SLOT(TMP_SLOT + 1), sizeof(double), g_pinc.stream), "norm");
+		pinc_check(pinc_hip_event_record(S->normEvent, g_pinc.stream), "norm");
+		if (*queued) {
+			int gslot = pinc_probe_begin(PINC_PROBE_GS);
+			pinc_check(pinc_hip_gs_sweep2x(S->phi[0], S->res[0], S->rho[0], S->L[0], g_pinc.stream), "gs sweep2x (ahead)");
+			pinc_probe_end(PINC_PROBE_GS, gslot, 24.0 * S->N[0]);
+		}
+		pinc_check(pinc_hip_event_sync(S->normEvent), "norm");
+	} else pinc_check(pinc_hip_d2h(S->hostNorm, PINC_SLOT(TMP_SLOT + 1), sizeof(double), g_pinc.stream), "norm");
+	return sqrt(*S->hostNorm / S->Ng0);
+}
+
+/* the solution to the caller's grid (replicated: phi[0] is its global
+ * array): the slab with its ghost planes (exact: within hz - 2 chunk of the
+ * owned planes); E reads the extended slab directly (gFinDiff1st) */
+static void copy_out(MultigridSolver *S, Grid *phi) {
+	phi->dev->ghostsValid = 0;
+	if (!S->shard) return;
+	long ps = S->ps0;
+	pinc_check(pinc_hip_d2d(phi->dev->d, S->phi[0] + (long)(S->hz - 1) * ps, ps * (S->nloc0 + 2) * sizeof(double),
+	                        g_pinc.stream),
+	           "shard phi");
+	phi->dev->ghostsValid = 1;
+	phi->dev->extStale = 0;
+}
+
+void mgSolve(MultigridSolver *S, Grid *rho, Grid *phi, const MpiInfo *mpiInfo) {
+	(void)mpiInfo;
+	pinc_phase_begin(4);
+	gather_rho(S, rho);
 	const int role = S->extrap ? S->role : PINC_MG_GUESS_WARM;
 	guess_begin(S, role);
 	if (S->nLevels > 1) {
-		/* the reference loops until converged (multigrid.c:1698); PINC_MG_MAX_CYCLES
-		 * caps a solve for diagnostics (stops with a warning) */
-		const long maxCycles = 1000000;
-		const char *capEnv = getenv("PINC_MG_MAX_CYCLES");
-		long cap = S->maxCycles ? S->maxCycles : (capEnv ? atol(capEnv) : 0);
+		/* V-cycles until pinc_mg_stop ends the solve (the reference: until converged, multigrid.c:1698) */
+		const long cap = S->maxCycles ? S->maxCycles : S->envCap;
 		double barRes = 2.;
 		long c = 0;
+		int stop = PINC_MG_CONTINUE, queued;
 		S->histN = 0;
 		if (S->native) neutralize_level(S, 0, S->rho[0]);
-		if (S->small) {
-			c = small_solve(S, cap, &barRes);
-			if (!(S->maxCycles && !isfinite(barRes)) && (!isfinite(barRes) || (c > maxCycles && barRes > 1.E-10)))
-				msg(ERROR, "multigrid did not converge (residual %g)", barRes);
-			if (!isfinite(barRes))
-				fprintf(stderr, "[pinc] rank %d solve stopped: residual %g after %ld cycles\n", g_pinc.rank, barRes, c);
-			else if (cap > 0 && c >= cap && barRes > 1.E-10)
-				fprintf(stderr, "[pinc] rank %d solve stopped at the PINC_MG_MAX_CYCLES cap (%ld), residual %.3e\n",
-				        g_pinc.rank, c, barRes);
-			barRes = 0; /* the loop below is the multi-launch form */
-		}
-		while (barRes > 1.E-10) {
-			if (S->useGraph) {
-				/* the V-cycle is a fixed launch sequence on fixed buffers:
-				 * captured once, then replayed (no per-kernel dispatch) */
-				if (!S->cycleGraph) {
-					g_pinc.capturing = 1;
-					pinc_check(pinc_hip_capture_begin(g_pinc.stream), "capture V-cycle");
-					vrec(S, 0);
-					pinc_check(pinc_hip_capture_end(g_pinc.stream, &S->cycleGraph), "capture V-cycle");
-					g_pinc.capturing = 0;
-				}
-				int gslot = pinc_probe_begin(PINC_PROBE_CYCLE);
-				pinc_check(pinc_hip_graph_launch(S->cycleGraph, g_pinc.stream), "V-cycle graph");
-				pinc_probe_end(PINC_PROBE_CYCLE, gslot, 0.0);
-			} else {
-				vrec(S, 0);
-			}
-			S->cycles++;
-			int nb = 0;
-			int slot = pinc_probe_begin(PINC_PROBE_RESIDUAL);
-			if (S->shard) {
-				/* owned planes, summed over the ranks */
-				pinc_check(pinc_hip_residual_sumsq_slab(S->phi[0], S->rho[0], S->L[0], S->hz, S->hz + S->nloc0,
-				                                        g_pinc.dScratch, &nb, g_pinc.stream),
-				           "residual norm");
-				pinc_probe_end(PINC_PROBE_RESIDUAL, slot, 16.0 * S->ps0 * S->nloc0);
-				pinc_check(pinc_hip_reduce(g_pinc.dScratch, nb, 1.0, PINC_SLOT(TMP_SLOT + 1), g_pinc.stream), "norm");
-				if (g_pinc.nranks > 1) pinc_comm_allreduce_sum(PINC_SLOT(TMP_SLOT + 1), 1, "norm");
-			} else {
-				pinc_check(pinc_hip_residual_sumsq(S->phi[0], S->rho[0], S->L[0], g_pinc.dScratch, &nb, g_pinc.stream),
-				           "residual norm");
-				pinc_probe_end(PINC_PROBE_RESIDUAL, slot, 16.0 * S->N[0]);
-				pinc_check(pinc_hip_reduce(g_pinc.dScratch, nb, 1.0, PINC_SLOT(TMP_SLOT + 1), g_pinc.stream), "norm");
-			}
-			double sum = 0;
-			int spec = 0;
-			if (S->speculate) {
-				/* the norm to pinned memory; while the host waits for it, the
-				 * next cycle's first double sweep (phi -> res: phi untouched)
-				 * runs if the last solve of this role needed another cycle */
-				pinc_check(pinc_hip_d2h_async(S->hostNorm, PINC_SLOT(TMP_SLOT + 1), sizeof(double), g_pinc.stream),
-				           "norm");
-				pinc_check(pinc_hip_event_record(S->normEvent, g_pinc.stream), "norm");
-				spec = first_sweep_is_double(S) && c + 1 < S->lastCycles[role & 3] && !S->swapped[0];
-				if (spec) {
-					int gslot = pinc_probe_begin(PINC_PROBE_GS);
-					pinc_check(pinc_hip_gs_sweep2x(S->phi[0], S->res[0], S->rho[0], S->L[0], g_pinc.stream),
-					           "gs sweep2x (ahead)");
-					pinc_probe_end(PINC_PROBE_GS, gslot, 24.0 * S->N[0]);
-				}
-				pinc_check(pinc_hip_event_sync(S->normEvent), "norm");
-				sum = *S->hostNorm;
-			} else {
-				pinc_check(pinc_hip_d2h(S->hostNorm, PINC_SLOT(TMP_SLOT + 1), sizeof(double), g_pinc.stream), "norm");
-				sum = *S->hostNorm;
-			}
-			barRes = sqrt(sum / S->Ng0);
+		if (S->small) stop = small_solve(S, cap, &c, &barRes);
+		while (stop == PINC_MG_CONTINUE) {
+			run_cycle(S);
+			c++;
+			barRes = residual_norm(S, c < S->lastCycles[role & 3], &queued);
 			if (S->histN < S->histCap) S->hist[S->histN] = barRes;
 			S->histN++;
-			if (S->maxCycles && !isfinite(barRes)) {
-				/* diagnostic run (mgSetLimit): keep the history, stop */
-				fprintf(stderr, "[pinc] rank %d solve stopped: residual %g after %ld cycles\n", g_pinc.rank, barRes, c + 1);
-				break;
-			}
-			if (++c > maxCycles || isnan(barRes)) msg(ERROR, "multigrid did not converge (residual %g)", barRes);
 			if (g_pinc.verbose && (c % g_pinc.verbose == 0)) {
 				fprintf(stderr, "[pinc] rank %d solve cycle %ld residual %.3e\n", g_pinc.rank, c, barRes);
 				fflush(stderr);
 			}
-			if (cap > 0 && c >= cap) {
-				fprintf(stderr, "[pinc] rank %d solve stopped at the PINC_MG_MAX_CYCLES cap (%ld), residual %.3e\n",
-				        g_pinc.rank, c, barRes);
-				break;
-			}
-			if (spec && barRes > 1.E-10) {
-				/* another cycle: its first double sweep is done (the
-				 * smoothing's ping-pong swap now) */
-				double *t = S->phi[0];
-				S->phi[0] = S->res[0];
-				S->res[0] = t;
-				S->swapped[0] ^= 1;
+			stop = pinc_mg_stop(barRes, c, cap, S->maxCycles != 0);
+			if (queued && stop == PINC_MG_CONTINUE) {
+				/* another cycle: its first double sweep is done, swap as smooth_native would */
+				pp_swap(S, 0);
 				S->preDone = 1;
 			}
 		}
-		S->preDone = 0;
+		report_stop(stop, barRes, c);
 		S->lastCycles[role & 3] = c;
 		if (S->native) neutralize_level(S, 0, S->phi[0]);
 	} else {
@@ -895,16 +905,6 @@ void mgSolve(MultigridSolver *S, Grid *rho, Grid *phi, const MpiInfo *mpiInfo) {
 	}
 	guess_end(S, role);
 	if (S->objects) S->role = PINC_MG_GUESS_WARM; /* mgGuessNext holds for one solve */
-	phi->dev->ghostsValid = 0;
-	if (S->shard) {
-		/* the slab with its ghost planes (exact: within hz - 2 chunk of the
-		 * owned planes); E reads the extended slab directly (gFinDiff1st) */
-		long ps = S->ps0;
-		pinc_check(pinc_hip_d2d(phi->dev->d, S->phi[0] + (long)(S->hz - 1) * ps, ps * (S->nloc0 + 2) * sizeof(double),
-		                        g_pinc.stream),
-		           "shard phi");
-		phi->dev->ghostsValid = 1;
-		phi->dev->extStale = 0;
-	}
+	copy_out(S, phi);
 	pinc_phase_end(4);
 }
