@@ -231,6 +231,16 @@ funPtr puDistr3D1_set(dictionary *ini);
 funPtr puDistrND1_set(dictionary *ini);
 void puDistr3D1(const Population *pop, Grid *rho);
 void puDistrND1(const Population *pop, Grid *rho);
+/* The first velocity moments of species s on the grid (an extension, not in
+ * the reference; definitions at pinc_hip_moments, include/pinc_hip.h), 1 to 3
+ * dimensions: mom, a grid of NM = 1 + nd + nd (nd + 1) / 2 values per node
+ * (gAlloc(ini, NM); msg(ERROR) otherwise), is zeroed and receives the CIC sums
+ * of 1, v_i, v_i v_j (i <= j) over the species' observable state (pSyncToHost's:
+ * a pending fused move is not applied, the velocities are the kicked ones).
+ * Ghost contributions are left unfolded, as puDistr leaves them: follow with
+ * gHaloOp(addSlice, mom, mpiInfo, FROMHALO).  The step's schedule is left as
+ * it was. */
+void puMomentsND1(Population *pop, int s, Grid *mom);
 funPtr puExtractEmigrants3D_set(dictionary *ini);
 funPtr puExtractEmigrantsND_set(dictionary *ini);
 void puExtractEmigrants3D(Population *pop, MpiInfo *mpiInfo);
@@ -384,6 +394,15 @@ int pinc_sim_pop_set(PincSim *sim, int s, long n, const double *pos, const doubl
 long pinc_sim_grid_shape(PincSim *sim, int which, int *size4);   /* 0 rho,1 phi,2 E */
 int pinc_sim_grid_get(PincSim *sim, int which, double *out);
 int pinc_sim_grid_set(PincSim *sim, int which, const double *in);
+/* Velocity moments (puMomentsND1): size4 = {NM, Tx, Ty, nloc} (1 for unused
+ * dimensions) of this rank's true nodes, the return value their product;
+ * pinc_sim_moments deposits species s, folds the halo and copies the true
+ * nodes [nloc][Ty][Tx][NM] to out.  pinc_sim_op(sim, "moments") computes
+ * every species' folded moments into the simulation's grids, and
+ * diagnostics:moments = N in the ini writes them every N-th step to
+ * <files:output>_moments<s>.grid.h5 (regular(), pinc_sim_write_output). */
+long pinc_sim_moments_shape(PincSim *sim, int *size4);
+int pinc_sim_moments(PincSim *sim, int s, double *out);
 int pinc_sim_emigrants(PincSim *sim, long *nEmigrants);
 int pinc_sim_species(PincSim *sim, double *charge, double *mass);
 int pinc_sim_sync(PincSim *sim);

@@ -279,6 +279,24 @@ int pinc_hip_import(pinc_pop_t pop, int s, long dst, const double *buf, long cap
  * reference's 1/q, q rescaling with pinc_hip_scale). */
 int pinc_hip_deposit(pinc_pop_t pop, int s, pinc_geom_t g, double *rhoSlab, void *stream);
 
+/* The first velocity moments of species s on the grid (an extension, not in
+ * the reference), with the CIC weights w_j(x_p) of puDistr3D1 / puDistrND1
+ * (particle p, node j).  Per node NM(nd) = 1 + nd + nd (nd + 1) / 2 doubles
+ * (10, 6, 3), value-major as E holds its three:
+ *   M[0]           = sum_p w_j(x_p)                  number per node
+ *   M[1 + i]       = sum_p w_j(x_p) v_p,i            i < nd
+ *   M[1 + nd + k]  = sum_p w_j(x_p) v_p,i v_p,j      i <= j, row-major upper
+ *                    triangle: xx xy xz yy yz zz (3-D), xx xy yy (2-D), xx
+ * Raw sums in code units (cells, cells per step), no charge or mass factor;
+ * g.literal is ignored.  Positions are pop.x; v[d] are the velocity arrays
+ * to read, indexed like pop.v[d] (pop.v itself in the plain case; element 0
+ * 16-byte aligned, as pop.v[d]).  Accumulates into momSlab (a slab grid of NM
+ * values per node, not zeroed here); the slab's ghost planes are left to the
+ * caller's fold (pinc_hip_fold_self_values).  Precondition as
+ * pinc_hip_deposit: every live particle's cell is in 0..T_d per dimension (a
+ * cell outside is clamped to that range). */
+int pinc_hip_moments(pinc_pop_t pop, int s, pinc_geom_t g, const double *const v[3], double *momSlab, void *stream);
+
 /* E as the reference holds it while species s is accelerated: its sequence
  * of in-place gMul(E, q/m) ... gMul(E, m/q) (pusher.c:192,212) gives
  * Es = E*pre; for t<s: Es = (Es*qm[t])*mq[t]; Es *= qm[s] (same rounding).
@@ -332,6 +350,8 @@ int pinc_hip_scale2(double *a, long n, double f1, double f2, void *stream);
 /* gHaloOp(addSlice, rho, FROMHALO) along the slab dim for a self-periodic
  * slab (grid.c:340-406): plane 0 += into nloc, plane nloc+1 += into 1 */
 int pinc_hip_fold_self(double *slab, pinc_geom_t g, void *stream);
+/* the same for a value-major slab of nValues doubles per node */
+int pinc_hip_fold_self_values(double *slab, pinc_geom_t g, int nValues, void *stream);
 /* a += b elementwise (gAddTo, grid.c:781-789) */
 int pinc_hip_add(double *a, const double *b, long n, void *stream);
 /* every slab node (incl. ghost planes) from the global periodic grid:

@@ -109,6 +109,8 @@ _sigs = {
     "pinc_sim_grid_shape": (C.c_long, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "pinc_sim_grid_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pinc_sim_grid_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pinc_sim_moments_shape": (C.c_long, [C.c_void_p, C.POINTER(C.c_int)]),
+    "pinc_sim_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pinc_sim_emigrants": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pinc_sim_species": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pinc_sim_sync": (C.c_int, [C.c_void_p]),

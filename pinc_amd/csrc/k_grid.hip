@@ -240,6 +240,18 @@ extern "C" int pinc_hip_fold_self(double *slab, pinc_geom_t g, void *stream) {
 	return check_launch("fold_self");
 }
 
+extern "C" int pinc_hip_fold_self_values(double *slab, pinc_geom_t g, int nValues, void *stream) {
+	if (nValues < 1) return set_error(hipErrorInvalidValue, "fold_self_values: nValues < 1");
+	long ps = plane_size(g) * nValues;
+	hipStream_t st = (hipStream_t)stream;
+	// pinc_hip_fold_self with nValues doubles per node (value-major: a plane
+	// is contiguous), the same order of the two adds
+	hipLaunchKernelGGL(k_add_plane, dim3(grid_for(ps)), dim3(kThreads), 0, st, slab + ps,
+	                   slab + (long)(g.nloc + 1) * ps, ps);
+	hipLaunchKernelGGL(k_add_plane, dim3(grid_for(ps)), dim3(kThreads), 0, st, slab + (long)g.nloc * ps, slab, ps);
+	return check_launch("fold_self_values");
+}
+
 extern "C" int pinc_hip_add(double *a, const double *b, long n, void *stream) {
 	if (n <= 0) return 0;
 	hipLaunchKernelGGL(k_add_plane, dim3(grid_for(n)), dim3(kThreads), 0, (hipStream_t)stream, a, b, n);

@@ -7,6 +7,8 @@
 //                       which emigrants are listed (DESIGN.md "Migration")
 //   import              shiftImmigrants + importParticles (pusher.c:941-985)
 //   deposit             puDistr3D1 / puDistrND1 (pusher.c:512-638)
+//   moments             per-species velocity moments with the deposit's
+//                       weights (an extension, not in the reference)
 //   accelerate          puAcc3D1KE / puAccND1KE + interpolators
 //                       (pusher.c:178-265, 1089-1162)
 //   init                pPosLattice / pPosPerturb / pVel* (population.c)
@@ -667,6 +669,267 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
 			off += node_off(G, d, blo[d] + c);
 		}
 		unsafeAtomicAdd(&rho[off], v);
+	}
+}
+
+// ---------------------------------------------------------- moments -------
+// The first velocity moments of one species on the grid (not in the
+// reference; include/pinc_hip.h has the definitions): per node NM = 1 + nd +
+// nd (nd + 1) / 2 sums of CIC weight times 1, v_i, v_i v_j (i <= j), value-major.
+// The deposit's structure with three differences (DESIGN.md "Moments"):
+//  * a node is NM doubles, so the LDS box holds kMomLds / NM nodes (640 in
+//    3-D, 50 KiB: three workgroups per CU).  A chunk whose cells' bounding
+//    box fits uses it; otherwise the box is a fixed shape around the chunk's
+//    mean cell (what a tile-sorted chunk spans after some steps of decay) and
+//    the runs outside it go to global memory, so stragglers cost their own
+//    atomics and not the whole chunk's LDS path;
+//  * a run of particles in one cell is summed in registers for GM moments at
+//    a time (2^nd GM <= 32 accumulators), in ceil(NM / GM) passes over the
+//    thread's particles, which are read again (from cache) in each pass: 80
+//    accumulators in one pass would not fit the register budget of two waves
+//    per SIMD;
+//  * the box is flushed value by value in storage order, so a wave's global
+//    atomics cover the contiguous NM values of neighbouring nodes.
+// geom.literal is ignored.  Cells are clamped to the slab (0..T_d), so that a
+// particle outside the frame cannot be deposited outside the array.
+constexpr int kMomItems = 16;
+constexpr int kMomChunk = kThreads * kMomItems;
+constexpr int kMomLds = 6400;  // doubles per workgroup
+__constant__ int kMomBox[3][3] = {{2048, 1, 1}, {32, 32, 1}, {11, 7, 7}};  // nodes, by nd
+
+template <int ND>
+__global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__ x0, const double *__restrict__ x1,
+                                                      const double *__restrict__ x2, const double *__restrict__ v0,
+                                                      const double *__restrict__ v1, const double *__restrict__ v2,
+                                                      long b0, long n, pinc_geom_t g, double *__restrict__ mom) {
+	constexpr int NC = 1 << ND;
+	constexpr int NM = 1 + ND + ND * (ND + 1) / 2;
+	constexpr int GM = (32 / NC < NM) ? 32 / NC : NM;
+	constexpr int NG = (NM + GM - 1) / GM;
+	constexpr int CAP = kMomLds / NM;  // nodes of the LDS box
+	static_assert(NG <= 3, "moment passes");
+	__shared__ double acc[kMomLds];
+	__shared__ int red[3 * 3 * (kThreads / 64) + (kThreads / 64)];
+	__shared__ int box[7];
+	Geo G = make_geo(g);
+	const double *xs[3] = {x0, x1, x2};
+	const double *vs[3] = {v0, v1, v2};
+	const long end = b0 + n;
+	const long i0 = (b0 & ~1L) + (long)blockIdx.x * kMomChunk + (long)threadIdx.x * kMomItems;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	constexpr int NW = kThreads / 64;
+	auto load2 = [&](const double *p, int k, double &a, double &b) {
+		long i = i0 + k;
+		if (i >= b0 && i + 1 < end) {
+			double2 v = *reinterpret_cast<const double2 *>(p + i);
+			a = v.x;
+			b = v.y;
+		} else {
+			a = (i >= b0 && i < end) ? p[i] : 0.0;
+			b = (i + 1 >= b0 && i + 1 < end) ? p[i + 1] : 0.0;
+		}
+	};
+	// cell of a position, kept inside the slab
+	auto cell_of = [&](int d, double x) { return min(max((int)x, 0), G.T[d]); };
+	unsigned valid = 0;
+#pragma unroll
+	for (int k = 0; k < kMomItems; k++) valid |= (unsigned)(i0 + k >= b0 && i0 + k < end) << k;
+
+	// pass 0: bounding box and mean of the chunk's cells
+	int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, sum[3] = {0, 0, 0};
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+#pragma unroll
+		for (int k = 0; k < kMomItems; k += 2) {
+			double a, b;
+			load2(xs[d], k, a, b);
+			if ((valid >> k) & 1u) {
+				const int c = cell_of(d, a);
+				lo[d] = min(lo[d], c);
+				hi[d] = max(hi[d], c + 1);
+				sum[d] += c;
+			}
+			if ((valid >> (k + 1)) & 1u) {
+				const int c = cell_of(d, b);
+				lo[d] = min(lo[d], c);
+				hi[d] = max(hi[d], c + 1);
+				sum[d] += c;
+			}
+		}
+	}
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+		int a = wave_min_i(lo[d]), b = wave_max_i(hi[d]), c = wave_sum_i(sum[d]);
+		if (lane == 0) {
+			red[(3 * d) * NW + wv] = a;
+			red[(3 * d + 1) * NW + wv] = b;
+			red[(3 * d + 2) * NW + wv] = c;
+		}
+	}
+	{
+		int c = wave_sum_i(__popc(valid));
+		if (lane == 0) red[9 * NW + wv] = c;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		int cnt = 0;
+		for (int w = 0; w < NW; w++) cnt += red[9 * NW + w];
+		long vol = 1;
+		int a[3], b[3], m[3];
+		for (int d = 0; d < ND; d++) {
+			a[d] = INT32_MAX, b[d] = INT32_MIN, m[d] = 0;
+			for (int w = 0; w < NW; w++) {
+				a[d] = min(a[d], red[(3 * d) * NW + w]);
+				b[d] = max(b[d], red[(3 * d + 1) * NW + w]);
+				m[d] += red[(3 * d + 2) * NW + w];
+			}
+			vol *= (long)(b[d] - a[d] + 1);
+		}
+		if (cnt > 0 && vol > CAP) {
+			// the fixed box around the mean cell; what lies outside goes to
+			// global memory
+			vol = 1;
+			for (int d = 0; d < ND; d++) {
+				const int e = kMomBox[ND - 1][d];
+				a[d] = m[d] / cnt - (e - 2) / 2;
+				b[d] = a[d] + e - 1;
+				vol *= e;
+			}
+		}
+		for (int d = 0; d < ND; d++) {
+			box[d] = a[d];
+			box[3 + d] = b[d] - a[d] + 1;
+		}
+		box[6] = cnt > 0 ? (int)vol : 0;
+	}
+	__syncthreads();
+	const int vol = box[6];
+	if (!vol) return;  // (no live particle in this chunk)
+
+	int blo[3] = {0, 0, 0}, st[3] = {0, 0, 0}, bn[3] = {1, 1, 1};
+	{
+		int sz = 1;
+#pragma unroll
+		for (int d = 0; d < ND; d++) {
+			blo[d] = box[d];
+			bn[d] = box[3 + d];
+			st[d] = sz;
+			sz *= bn[d];
+		}
+	}
+	for (int t = threadIdx.x; t < vol * NM; t += kThreads) acc[t] = 0.0;
+	__syncthreads();
+	int coff[NC];
+#pragma unroll
+	for (int c = 0; c < NC; c++) {
+		coff[c] = 0;
+#pragma unroll
+		for (int d = 0; d < ND; d++) coff[c] += ((c >> d) & 1) ? st[d] : 0;
+	}
+
+	// passes 1..NG: moments [gm * GM, gm * GM + GM) of runs of equal cells
+	auto pass = [&](auto gc) {
+		constexpr int M0 = decltype(gc)::value * GM;
+		constexpr int MN = (M0 + GM <= NM) ? GM : NM - M0;
+		int cj[3] = {INT32_MIN, 0, 0};
+		double a[NC][MN];
+#pragma unroll
+		for (int c = 0; c < NC; c++)
+#pragma unroll
+			for (int q = 0; q < MN; q++) a[c][q] = 0.0;
+		auto flush = [&]() {
+			if (cj[0] == INT32_MIN) return;
+			bool in = true;
+			int l0 = 0;
+#pragma unroll
+			for (int d = 0; d < ND; d++) {
+				const int r = cj[d] - blo[d];
+				in = in && r >= 0 && r + 1 < bn[d];
+				l0 += r * st[d];
+			}
+			if (in) {
+#pragma unroll
+				for (int c = 0; c < NC; c++)
+#pragma unroll
+					for (int q = 0; q < MN; q++) atomicAdd(&acc[(l0 + coff[c]) * NM + M0 + q], a[c][q]);
+			} else {
+#pragma unroll
+				for (int c = 0; c < NC; c++) {
+					double *p = mom + corner_off<ND>(G, cj, c) * NM + M0;
+#pragma unroll
+					for (int q = 0; q < MN; q++) unsafeAtomicAdd(p + q, a[c][q]);
+				}
+			}
+		};
+#pragma unroll 2
+		for (int k = 0; k < kMomItems; k += 2) {
+			double pp[3][2], pv[3][2];
+#pragma unroll
+			for (int d = 0; d < ND; d++) {
+				load2(xs[d], k, pp[d][0], pp[d][1]);
+				load2(vs[d], k, pv[d][0], pv[d][1]);
+			}
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				if (!((valid >> (k + h)) & 1u)) continue;
+				double dec[3], comp[3], w[NC], f[NM];
+				int j[3];
+				bool same = true;
+#pragma unroll
+				for (int d = 0; d < ND; d++) {
+					j[d] = cell_of(d, pp[d][h]);
+					dec[d] = pp[d][h] - j[d];
+					comp[d] = 1 - dec[d];
+					same = same && (j[d] == cj[d]);
+				}
+				cic_weights<ND, ND == 3>(dec, comp, w);
+				// 1, v_i, v_i v_j (i <= j, row-major upper triangle)
+				f[0] = 1.0;
+				{
+					int m = 1 + ND;
+#pragma unroll
+					for (int d = 0; d < ND; d++) f[1 + d] = pv[d][h];
+#pragma unroll
+					for (int d = 0; d < ND; d++)
+#pragma unroll
+						for (int e = d; e < ND; e++) f[m++] = pv[d][h] * pv[e][h];
+				}
+				if (!same) {
+					flush();
+#pragma unroll
+					for (int c = 0; c < NC; c++)
+#pragma unroll
+						for (int q = 0; q < MN; q++) a[c][q] = 0.0;
+#pragma unroll
+					for (int d = 0; d < ND; d++) cj[d] = j[d];
+				}
+#pragma unroll
+				for (int c = 0; c < NC; c++)
+#pragma unroll
+					for (int q = 0; q < MN; q++) a[c][q] += w[c] * f[M0 + q];
+			}
+		}
+		flush();
+	};
+	pass(std::integral_constant<int, 0>{});
+	if constexpr (NG > 1) pass(std::integral_constant<int, 1>{});
+	if constexpr (NG > 2) pass(std::integral_constant<int, 2>{});
+	__syncthreads();
+
+	// flush the box: values in storage order, one global atomic per touched value
+	for (int t = threadIdx.x; t < vol * NM; t += kThreads) {
+		const double v = acc[t];
+		if (v == 0.0) continue;
+		int r = t / NM;
+		const int m = t - r * NM;
+		long off = 0;
+#pragma unroll
+		for (int d = 0; d < ND; d++) {
+			int c = r % bn[d];
+			r /= bn[d];
+			off += node_off(G, d, blo[d] + c);
+		}
+		unsafeAtomicAdd(&mom[off * NM + m], v);
 	}
 }
 
@@ -2866,6 +3129,28 @@ extern "C" int pinc_hip_deposit(pinc_pop_t pop, int s, pinc_geom_t g, double *rh
 	else
 		hipLaunchKernelGGL((k_deposit_tiled<1, false>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, b0, n, g, rho);
 	return check_launch("deposit");
+}
+
+extern "C" int pinc_hip_moments(pinc_pop_t pop, int s, pinc_geom_t g, const double *const v[3], double *momSlab,
+                                void *stream) {
+	if (g.nd < 1 || g.nd > 3 || s < 0 || s >= PINC_MAX_SPECIES || !v || !momSlab)
+		return set_error(hipErrorInvalidValue, "moments: bad species, dimensions or null array");
+	for (int d = 0; d < g.nd; d++)
+		if (!pop.x[d] || !v[d]) return set_error(hipErrorInvalidValue, "moments: null particle array");
+	long n = pop.iStop[s] - pop.iStart[s];
+	if (n <= 0) return 0;
+	long b0 = pop.iStart[s];
+	long nb = ceil_div(n + (b0 & 1L), (long)kMomChunk);
+	hipStream_t st = (hipStream_t)stream;
+	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr, *x2 = g.nd > 2 ? pop.x[2] : nullptr;
+	const double *v1 = g.nd > 1 ? v[1] : nullptr, *v2 = g.nd > 2 ? v[2] : nullptr;
+	if (g.nd == 3)
+		hipLaunchKernelGGL((k_moments<3>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
+	else if (g.nd == 2)
+		hipLaunchKernelGGL((k_moments<2>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
+	else
+		hipLaunchKernelGGL((k_moments<1>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
+	return check_launch("moments");
 }
 
 extern "C" int pinc_hip_field_chain_all(const double *E, double *Es, long n, const double *qm, const double *mq,

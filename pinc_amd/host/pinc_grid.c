@@ -298,7 +298,10 @@ void gHaloOp(funPtr sliceOp, Grid *grid, const MpiInfo *mpiInfo, opDirection dir
 		dv->folds++;
 		pinc_grid_touch(grid);
 		if (g_pinc.nranks == 1) {
-			pinc_check(pinc_hip_fold_self(dv->d, geo, g_pinc.stream), "fold");
+			if (dv->nValues > 1)
+				pinc_check(pinc_hip_fold_self_values(dv->d, geo, dv->nValues, g_pinc.stream), "fold");
+			else
+				pinc_check(pinc_hip_fold_self(dv->d, geo, g_pinc.stream), "fold");
 		} else {
 			/* ghost nloc+1 goes up and lands on the upper rank's plane 1;
 			 * ghost 0 goes down and lands on the lower rank's plane nloc */

@@ -1103,6 +1103,60 @@ void pinc_literal_second_fold(const Population *pop, Grid *rho, int order) {
 	pinc_check(pinc_hip_add(g->d, g->lit, g->n, g_pinc.stream), "second fold add");
 }
 
+/* ------------------------------------------------------------- moments -- */
+/* The first velocity moments of species s on the grid (pinc_hip_moments; an
+ * extension, not in the reference): mom = 0, then the deposit of the
+ * observable state, as pSyncToHost defines it.  With a fused push pending
+ * that is the pre-move positions (p.x) and the kicked velocities, read where
+ * they already are: p.v (a push in place, or a sorting push whose kick was
+ * materialised), altV (a species the sorting push left in order), or a
+ * temporary filled by pinc_pending_vel (a species whose sorting push is
+ * pending).  No state of the schedule changes.  Ghost contributions are left
+ * unfolded, as puDistr leaves them: gHaloOp(addSlice, mom, mpiInfo, FROMHALO)
+ * folds them.  mom never takes part in the literal second fold. */
+void puMomentsND1(Population *pop, int s, Grid *mom) {
+	pinc_pop_flush_host(pop);
+	PincDevPop *dv = pop->dev;
+	PincDevGrid *g = mom->dev;
+	const int nd = pop->nDims, nm = 1 + nd + nd * (nd + 1) / 2;
+	if (s < 0 || s >= pop->nSpecies) msg(ERROR, "puMomentsND1: species %d out of range", s);
+	if (g->nValues != nm)
+		msg(ERROR, "puMomentsND1 needs a grid of %d values per node (gAlloc(ini, %d)), not %d", nm, nm, g->nValues);
+	pinc_grid_touch(mom);
+	pinc_check(pinc_hip_zero(g->d, g->n, g_pinc.stream), "moments zero");
+	g->ghostsValid = 0;
+	g->depPop = NULL;
+	g->folds = 0;
+	const long a = pop->iStart[s], n = pop->iStop[s] - a;
+	if (n <= 0) return;
+	pinc_pop_t p = pinc_devpop(pop);
+	const double *v[3] = {p.v[0], p.v[1], p.v[2]};
+	double *tmp = NULL;
+	if (dv->pending && dv->pendingSorted) {
+		if (dv->permId[s]) {
+			for (int d = 0; d < nd; d++) v[d] = dv->altV[d];
+		} else if (!dv->vKicked[s]) {
+			/* (n + 2 per component, the first at an index of a's parity: the
+			 * kernel's 16-byte loads stay aligned) */
+			const long pitch = (n + 3) & ~1L;
+			pinc_check(pinc_hip_malloc((void **)&tmp, nd * pitch * sizeof(double)), "moments velocities");
+			double *dst[3] = {NULL, NULL, NULL};
+			for (int d = 0; d < nd; d++) {
+				dst[d] = tmp + d * pitch + (a & 1L);
+				v[d] = dst[d] - a;
+			}
+			pinc_pending_vel(pop, s, dst);
+		}
+	}
+	pinc_geom_t geo = g->geom;
+	geo.literal = 0;
+	pinc_check(pinc_hip_moments(p, s, geo, v, g->d, g_pinc.stream), "moments");
+	if (tmp) {
+		pinc_check(pinc_hip_stream_sync(g_pinc.stream), "moments");
+		pinc_hip_free(tmp);
+	}
+}
+
 void puDistr3D1(const Population *pop, Grid *rho) { distr(pop, rho); }
 void puDistrND1(const Population *pop, Grid *rho) { distr(pop, rho); }
 

@@ -55,6 +55,11 @@ struct PincSim {
 	PincObj *obj;      /* immersed object (objects:sphere), or NULL */
 	int output;        /* pinc_sim_open_output ran: files below are open */
 	long long history;
+	/* velocity moments (puMomentsND1): one grid of NM values per species,
+	 * allocated when diagnostics:moments > 0 or at the first request */
+	Grid *mom[PINC_MAX_SPECIES];
+	int momEvery;      /* diagnostics:moments = N: written every N-th step (0: off) */
+	int momOutput;     /* their files are open */
 };
 
 static int g_simActive = 0;
@@ -73,6 +78,50 @@ static void check_errors(void) {
 	g_pinc.errRead = g_pinc.errSerial;
 	pinc_check(pinc_hip_d2h(&err, g_pinc.dErr, sizeof(int), g_pinc.stream), "assert word");
 	report_errors(err);
+}
+
+/* ------------------------------------------------------------ moments -- */
+static void mom_alloc(PincSim *S) {
+	const int nd = S->pop->nDims;
+	for (int s = 0; s < S->pop->nSpecies; s++)
+		if (!S->mom[s]) S->mom[s] = gAlloc(S->ini, 1 + nd + nd * (nd + 1) / 2);
+}
+
+/* species s's moments of the observable state, halo folded, in S->mom[s] */
+static void mom_compute(PincSim *S, int s) {
+	mom_alloc(S);
+	puMomentsND1(S->pop, s, S->mom[s]);
+	gHaloOp((funPtr)addSlice, S->mom[s], S->mpi, FROMHALO);
+}
+
+static void mom_open(PincSim *S) {
+	if (S->momOutput || S->momEvery <= 0) return;
+	mom_alloc(S);
+	for (int s = 0; s < S->pop->nSpecies; s++) {
+		char name[32];
+		snprintf(name, sizeof(name), "moments%d", s);
+		gOpenH5(S->ini, S->mom[s], S->mpi, S->units, 1., name);
+	}
+	S->momOutput = 1;
+}
+
+static void mom_write(PincSim *S, double n) {
+	if (S->momEvery <= 0 || (long)n % S->momEvery != 0) return;
+	mom_open(S);
+	for (int s = 0; s < S->pop->nSpecies; s++) {
+		mom_compute(S, s);
+		gWriteH5(S->mom[s], S->mpi, n);
+	}
+}
+
+static void mom_free(PincSim *S) {
+	for (int s = 0; s < PINC_MAX_SPECIES; s++) {
+		if (!S->mom[s]) continue;
+		if (S->momOutput) gCloseH5(S->mom[s]);
+		gFree(S->mom[s]);
+		S->mom[s] = NULL;
+	}
+	S->momOutput = 0;
 }
 
 static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
@@ -134,6 +183,9 @@ static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
 	gCreateNeighborhood(ini, S->mpi, S->rho);
 	gSetBndSlices(S->phi, S->mpi);
 	g_pinc.maxVel = iniHas(ini, "population:maxVel") ? iniGetDouble(ini, "population:maxVel") : INFINITY;
+	S->momEvery = iniHas(ini, "diagnostics:moments") ? iniGetInt(ini, "diagnostics:moments") : 0;
+	if (S->momEvery < 0) msg(ERROR, "diagnostics:moments must be >= 0");
+	if (S->momEvery > 0) mom_alloc(S);
 	return S;
 }
 
@@ -264,11 +316,13 @@ static void output_write(PincSim *S, double n) {
 	gWriteH5(S->phi, S->mpi, n);
 	pWriteH5(S->pop, S->mpi, n, n + 0.5);
 	pWriteEnergy(S->history, S->pop, n);
+	mom_write(S, n);
 }
 
 static void sim_free(PincSim *S) {
 	if (!S) return;
 	output_close(S);
+	mom_free(S);
 	pinc_obj_free(S->obj);
 	if (S->solverFree) S->solverFree(S->solver);
 	gFree(S->E);
@@ -300,6 +354,7 @@ void regular(dictionary *ini) {
 		pinc_sim_energy(S, &ke, &pe, NULL);
 		msg(STATUS, "KE %.17g PE %.17g", ke, pe);
 		if (h5) output_write(S, (double)n);
+		else mom_write(S, (double)n);
 	}
 	S->ini = NULL; /* owned by the caller */
 	sim_free(S);
@@ -369,6 +424,8 @@ int pinc_sim_op(PincSim *S, const char *op) {
 	else if (!strcmp(op, "energy")) {
 		pSumKinEnergy(S->pop);
 		gPotEnergy(S->rho, S->phi, S->pop);
+	} else if (!strcmp(op, "moments")) {
+		for (int s = 0; s < S->pop->nSpecies; s++) mom_compute(S, s);
 	} else if (!strcmp(op, "step")) sim_step(S);
 	else {
 		msg(WARNING, "unknown op %s", op);
@@ -474,6 +531,43 @@ int pinc_sim_grid_set(PincSim *S, int which, const double *in) {
 	if (!g->val) g->val = calloc(g->sizeProd[g->rank], sizeof(double));
 	memcpy(g->val, in, g->sizeProd[g->rank] * sizeof(double));
 	gSyncToDevice(g);
+	return 0;
+}
+
+long pinc_sim_moments_shape(PincSim *S, int *size4) {
+	const int nd = S->pop->nDims;
+	pinc_geom_t g = S->pop->dev->geom;
+	long n = size4[0] = 1 + nd + nd * (nd + 1) / 2;
+	for (int d = 0; d < 3; d++) {
+		size4[1 + d] = d < nd ? (d == nd - 1 ? g.nloc : g.T[d]) : 1;
+		n *= size4[1 + d];
+	}
+	return n;
+}
+
+int pinc_sim_moments(PincSim *S, int s, double *out) {
+	if (s < 0 || s >= S->pop->nSpecies) {
+		msg(WARNING, "pinc_sim_moments: species %d out of range", s);
+		return 1;
+	}
+	mom_compute(S, s);
+	Grid *g = S->mom[s];
+	gSyncToHost(g);
+	/* true nodes in C order [z][y][x][value], as gWriteH5 takes them */
+	const int nd = g->rank - 1, nv = g->size[0];
+	int T[3] = {1, 1, 1}, Sz[3] = {1, 1, 1}, G[3] = {0, 0, 0};
+	for (int d = 0; d < nd; d++) {
+		T[d] = g->trueSize[d + 1];
+		Sz[d] = g->size[d + 1];
+		G[d] = g->nGhostLayers[d + 1];
+	}
+	long o = 0;
+	for (int k = 0; k < T[2]; k++)
+		for (int j = 0; j < T[1]; j++)
+			for (int i = 0; i < T[0]; i++) {
+				const long node = (i + G[0]) + (long)Sz[0] * ((j + G[1]) + (long)Sz[1] * (k + G[2]));
+				for (int v = 0; v < nv; v++) out[o++] = g->val[node * nv + v];
+			}
 	return 0;
 }
 

@@ -171,6 +171,20 @@ class Sim:
         v = np.ascontiguousarray(values, dtype=np.float64).ravel()
         HOST.pinc_sim_grid_set(self._h, which, v.ctypes.data)
 
+    def moments(self, s: int) -> np.ndarray:
+        """The first velocity moments of species s on this rank's true nodes,
+        halo folded: shape true nodes + (NM,), [nz, ny, nx, 10] in 3-D (NM =
+        1 + nd + nd (nd + 1) / 2).  Per node the CIC-weighted sums of 1, v_i
+        and v_i v_j (i <= j: xx xy xz yy yz zz) over the species' particles
+        at (x_n, v_n+1/2), in code units; pinc_amd.moments.derive turns them
+        into density, bulk velocity, pressure and temperature."""
+        size = (C.c_int * 4)()
+        n = HOST.pinc_sim_moments_shape(self._h, size)
+        out = np.zeros(n)
+        if HOST.pinc_sim_moments(self._h, s, out.ctypes.data):
+            raise ValueError(f"moments: no species {s}")
+        return out.reshape(tuple(reversed(size[1:1 + self.ndims])) + (size[0],))
+
     def emigrants(self) -> np.ndarray:
         n = 3 ** self.ndims * self.nspecies
         out = np.zeros(n, dtype=np.int64)
