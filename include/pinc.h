@@ -241,6 +241,23 @@ void puDistrND1(const Population *pop, Grid *rho);
  * gHaloOp(addSlice, mom, mpiInfo, FROMHALO).  The step's schedule is left as
  * it was. */
 void puMomentsND1(Population *pop, int s, Grid *mom);
+/* Phase-space histogram of species s (an extension, not in the reference;
+ * the binning rule at pinc_hip_phase_hist, include/pinc_hip.h) over one or
+ * two of x y z vx vy vz (axis: PINC_PS_*, axis[1] = PINC_PS_NONE for one),
+ * nbins[a] equal bins over [lo[a], hi[a]).  The state is puMomentsND1's
+ * observable one; positions are in the global frame (local + offset, as
+ * pWriteH5 writes them), velocities in code units.  hist (host,
+ * nbins[1] * nbins[0] doubles, axis 0 fastest) receives the counts summed
+ * over the ranks and *outside the live particles outside the range: the call
+ * is collective, every rank gets the same.  The step's schedule is left as
+ * it was.  A bad axis, hi <= lo, nbins < 1 or more than 2^24 bins is
+ * msg(ERROR). */
+typedef struct {
+	int axis[2];
+	int nbins[2];
+	double lo[2], hi[2];
+} PhaseSpec;
+void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *mpiInfo, double *hist, double *outside);
 funPtr puExtractEmigrants3D_set(dictionary *ini);
 funPtr puExtractEmigrantsND_set(dictionary *ini);
 void puExtractEmigrants3D(Population *pop, MpiInfo *mpiInfo);
@@ -326,6 +343,12 @@ long long xyOpenH5(const dictionary *ini, const char *fName);
 void xyCreateDataset(long long h5, const char *name);
 void xyWrite(long long h5, const char *name, double x, double y, int op);
 void xyCloseH5(long long h5);
+/* <files:output>_<fName>.ps.h5 for puPhaseHist's histograms: file attributes
+ * axes, min, max; psWriteH5 adds the dataset /n=<n> [nbins1, nbins0] with the
+ * attribute outside (rank 0 writes the global histogram it is given) */
+long long psOpenH5(const dictionary *ini, const char *fName, const PhaseSpec *spec);
+void psWriteH5(long long h5, const PhaseSpec *spec, const double *hist, double outside, double n);
+void psCloseH5(long long h5);
 void pCreateEnergyDatasets(long long xy, Population *pop);
 void pWriteEnergy(long long xy, Population *pop, double x);
 int pinc_h5_available(void);
@@ -403,6 +426,16 @@ int pinc_sim_grid_set(PincSim *sim, int which, const double *in);
  * <files:output>_moments<s>.grid.h5 (regular(), pinc_sim_write_output). */
 long pinc_sim_moments_shape(PincSim *sim, int *size4);
 int pinc_sim_moments(PincSim *sim, int s, double *out);
+/* Phase-space histograms (puPhaseHist): pinc_sim_phase_hist fills hist
+ * (nbins[1] * nbins[0] doubles) and *outside for species s; non-zero (and a
+ * warning) for a bad species or spec.  pinc_sim_op(sim, "phase") takes the
+ * ini's histogram of every species, and diagnostics:phaseSpace = N (with
+ * phaseSpaceAxes, phaseSpaceBins, phaseSpaceMin, phaseSpaceMax) writes them
+ * every N-th step to <files:output>_phase<s>.ps.h5 (regular(),
+ * pinc_sim_write_output).  pinc_sim_offset: this rank's offset of the local
+ * to the global frame, nDims ints. */
+int pinc_sim_phase_hist(PincSim *sim, int s, const PhaseSpec *spec, double *hist, double *outside);
+int pinc_sim_offset(PincSim *sim, int *offset);
 int pinc_sim_emigrants(PincSim *sim, long *nEmigrants);
 int pinc_sim_species(PincSim *sim, double *charge, double *mass);
 int pinc_sim_sync(PincSim *sim);

@@ -297,6 +297,32 @@ int pinc_hip_deposit(pinc_pop_t pop, int s, pinc_geom_t g, double *rhoSlab, void
  * cell outside is clamped to that range). */
 int pinc_hip_moments(pinc_pop_t pop, int s, pinc_geom_t g, const double *const v[3], double *momSlab, void *stream);
 
+/* Phase-space histogram of species s over one or two of its coordinates (an
+ * extension, not in the reference).  The binning rule is fixed, so that it
+ * can be restated bit for bit (no fused multiply-add in this library): per
+ * axis a, with c the particle's coordinate,
+ *     t = ((c + shift[a]) - lo[a]) * scale[a]            in fp64, this order
+ * the particle is inside iff t >= 0 && t < nbins[a] on every axis (a NaN is
+ * outside), its bin is (int)t, and it adds 1 to hist[b1 * nbins[0] + b0];
+ * every other live particle adds 1 to *outside.  hist and outside are device
+ * memory and are accumulated, not cleared.  Only [iStart[s], iStop[s]) is
+ * read.  v[d] are the velocity arrays, as in pinc_hip_moments.  Errors: an
+ * axis that is no PINC_PS_*, a position or velocity axis >= pop.nd,
+ * nbins < 1, nbins[1] != 1 without a second axis, nbins[0] * nbins[1] > 2^24. */
+enum { PINC_PS_X = 0, PINC_PS_Y, PINC_PS_Z, PINC_PS_VX, PINC_PS_VY, PINC_PS_VZ, PINC_PS_NONE = -1 };
+typedef struct {
+	int axis[2];     /* PINC_PS_*; axis[1] = PINC_PS_NONE for a 1-D histogram */
+	int nbins[2];    /* nbins[1] = 1 when axis[1] is NONE */
+	double shift[2]; /* added to the coordinate first (global-frame offset for a position, 0 for a velocity) */
+	double lo[2];    /* lower edge */
+	double scale[2]; /* nbins / (hi - lo), computed once by the caller */
+} pinc_phase_t;
+int pinc_hip_phase_hist(pinc_pop_t pop, int s, const double *const v[3], pinc_phase_t spec, unsigned long long *hist,
+                        unsigned long long *outside, void *stream);
+/* counters of the kernel's LDS box: a chunk of particles whose bounding box
+ * in bin space has at most this area is counted in LDS (tests, the probe) */
+long pinc_hip_phase_lds_bins(void);
+
 /* E as the reference holds it while species s is accelerated: its sequence
  * of in-place gMul(E, q/m) ... gMul(E, m/q) (pusher.c:192,212) gives
  * Es = E*pre; for t<s: Es = (Es*qm[t])*mq[t]; Es *= qm[s] (same rounding).

@@ -17,6 +17,11 @@ NPHASES = 8
 PHASES = ["move", "extract", "migrate", "deposit", "solve", "efield", "accelerate", "energy"]
 
 
+class PhaseSpec(C.Structure):
+    """PhaseSpec (include/pinc.h)"""
+    _fields_ = [("axis", C.c_int * 2), ("nbins", C.c_int * 2), ("lo", C.c_double * 2), ("hi", C.c_double * 2)]
+
+
 class PincSimOpts(C.Structure):
     _fields_ = [
         ("literal", C.c_int),
@@ -111,6 +116,8 @@ _sigs = {
     "pinc_sim_grid_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "pinc_sim_moments_shape": (C.c_long, [C.c_void_p, C.POINTER(C.c_int)]),
     "pinc_sim_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "pinc_sim_phase_hist": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PhaseSpec), C.c_void_p, C.POINTER(C.c_double)]),
+    "pinc_sim_offset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pinc_sim_emigrants": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pinc_sim_species": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pinc_sim_sync": (C.c_int, [C.c_void_p]),

@@ -9,7 +9,9 @@
 //   deposit             puDistr3D1 / puDistrND1 (pusher.c:512-638)
 //   moments             per-species velocity moments with the deposit's
 //                       weights (an extension, not in the reference)
-//   accelerate          puAcc3D1KE / puAccND1KE + interpolators
+//   phase space         per-species histograms over one or two coordinates
+//                       (an extension, not in the reference)
+//   accelerate         puAcc3D1KE / puAccND1KE + interpolators
 //                       (pusher.c:178-265, 1089-1162)
 //   init                pPosLattice / pPosPerturb / pVel* (population.c)
 //
@@ -930,6 +932,159 @@ __global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__
 			off += node_off(G, d, blo[d] + c);
 		}
 		unsafeAtomicAdd(&mom[off * NM + m], v);
+	}
+}
+
+// ------------------------------------------------------ phase space -------
+// Histogram of one species over NA = 1 or 2 of its coordinates (not in the
+// reference; include/pinc_hip.h has the binning rule).  The deposit's frame:
+// a workgroup owns kPhChunk consecutive particles, a thread kPhItems of them,
+// loaded as 16-byte pairs from the one or two arrays the spec names.
+//  * pass 0 bins the thread's particles (the bins stay in registers) and
+//    finds the chunk's bounding box in bin space from the inside particles;
+//  * a box of at most kPhLds bins is counted in LDS with 32-bit counters (a
+//    chunk has 4096 particles: no overflow) and flushed with one 64-bit
+//    global atomic per non-zero counter.  A small box is kept in up to
+//    kPhCopies copies, lane & (copies - 1) picks one (odd stride: the copies
+//    of a bin lie in different banks), as the push keeps its charge box: f(v)
+//    puts most of a wave into a few bins, and same-address LDS atomics
+//    serialise inside a wave.  The flush sums the copies;
+//  * a box that does not fit: one 64-bit global atomic per inside particle.
+// Outside particles are counted per thread, summed per wave and added with
+// one atomic per workgroup.
+constexpr int kPhItems = 16;
+constexpr int kPhChunk = kThreads * kPhItems;
+// Measured at 128^3, 64 ppc (tools/phase_probe.py, profiles/phase_space.json):
+// 4096, 8192 and 16384 counters take 7.73, 6.94 and 6.21 ms over the six
+// probed cases (16384 halves (x, vx) after 8 steps without a sort, 1.99 ->
+// 0.99 ms, and costs 0.1 ms where 8192 already fits); 1, 4, 8 or 16 copies
+// are within the noise of each other (f(vx) 0.92-0.94 ms: its time is the
+// flush's atomics of every workgroup into the same 128 bins, not the LDS).
+constexpr int kPhLds = 16384;  // 32-bit counters of the LDS box (64 KiB: two workgroups per CU)
+constexpr int kPhCopies = 8;   // as the push's charge box
+
+template <int NA>
+__global__ __launch_bounds__(kThreads) void k_phase_hist(const double *__restrict__ c0, const double *__restrict__ c1,
+                                                         long b0, long n, pinc_phase_t sp,
+                                                         unsigned long long *__restrict__ hist,
+                                                         unsigned long long *__restrict__ outside) {
+	constexpr int NW = kThreads / 64;
+	__shared__ unsigned cnt[kPhLds + 1];
+	__shared__ int red[(2 * NA + 1) * NW];
+	__shared__ int box[6];
+	const double *cs[2] = {c0, c1};
+	const long end = b0 + n;
+	const long i0 = (b0 & ~1L) + (long)blockIdx.x * kPhChunk + (long)threadIdx.x * kPhItems;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	auto load2 = [&](const double *p, int k, double &a, double &b) {
+		long i = i0 + k;
+		if (i >= b0 && i + 1 < end) {
+			double2 v = *reinterpret_cast<const double2 *>(p + i);
+			a = v.x;
+			b = v.y;
+		} else {
+			a = (i >= b0 && i < end) ? p[i] : 0.0;
+			b = (i + 1 >= b0 && i + 1 < end) ? p[i + 1] : 0.0;
+		}
+	};
+	unsigned valid = 0;
+#pragma unroll
+	for (int k = 0; k < kPhItems; k++) valid |= (unsigned)(i0 + k >= b0 && i0 + k < end) << k;
+
+	// pass 0: the bins, and the chunk's bounding box of the inside particles
+	int bin[NA][kPhItems];
+	unsigned in = valid;
+#pragma unroll
+	for (int a = 0; a < NA; a++) {
+		const double shift = sp.shift[a], lo = sp.lo[a], scale = sp.scale[a], nb = (double)sp.nbins[a];
+#pragma unroll
+		for (int k = 0; k < kPhItems; k += 2) {
+			double c[2];
+			load2(cs[a], k, c[0], c[1]);
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				const double t = ((c[h] + shift) - lo) * scale;
+				const bool ok = t >= 0.0 && t < nb;
+				bin[a][k + h] = ok ? (int)t : 0;
+				if (!ok) in &= ~(1u << (k + h));
+			}
+		}
+	}
+	int lo[NA], hi[NA];
+#pragma unroll
+	for (int a = 0; a < NA; a++) {
+		lo[a] = INT32_MAX, hi[a] = INT32_MIN;
+#pragma unroll
+		for (int k = 0; k < kPhItems; k++)
+			if ((in >> k) & 1u) {
+				lo[a] = min(lo[a], bin[a][k]);
+				hi[a] = max(hi[a], bin[a][k]);
+			}
+	}
+#pragma unroll
+	for (int a = 0; a < NA; a++) {
+		const int x = wave_min_i(lo[a]), y = wave_max_i(hi[a]);
+		if (lane == 0) {
+			red[(2 * a) * NW + wv] = x;
+			red[(2 * a + 1) * NW + wv] = y;
+		}
+	}
+	{
+		const int o = wave_sum_i(__popc(valid & ~in));
+		if (lane == 0) red[2 * NA * NW + wv] = o;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		int out = 0;
+		for (int w = 0; w < NW; w++) out += red[2 * NA * NW + w];
+		if (out) atomicAdd(outside, (unsigned long long)out);
+		long area = 1;
+		bool any = true;
+		box[1] = 0, box[3] = 1;
+		for (int a = 0; a < NA; a++) {
+			int x = INT32_MAX, y = INT32_MIN;
+			for (int w = 0; w < NW; w++) {
+				x = min(x, red[(2 * a) * NW + w]);
+				y = max(y, red[(2 * a + 1) * NW + w]);
+			}
+			any = any && y >= x;
+			if (!any) break;
+			box[a] = x;
+			box[2 + a] = y - x + 1;
+			area *= (long)(y - x + 1);
+		}
+		// 0: no inside particle; -1: the box does not fit; else its area
+		box[4] = !any ? 0 : area <= kPhLds ? (int)area : -1;
+		int nc = 1;
+		if (any && area <= kPhLds)
+			while (nc < kPhCopies && 2 * nc * ((int)area | 1) <= kPhLds + 1) nc *= 2;
+		box[5] = nc;
+	}
+	__syncthreads();
+	const int area = box[4];
+	if (!area) return;
+	const long nb0 = sp.nbins[0];
+	if (area < 0) {
+#pragma unroll
+		for (int k = 0; k < kPhItems; k++)
+			if ((in >> k) & 1u) atomicAdd(&hist[(NA > 1 ? bin[NA - 1][k] * nb0 : 0L) + bin[0][k]], 1ull);
+		return;
+	}
+	const int lo0 = box[0], lo1 = box[1], w0 = box[2], nCopy = box[5];
+	const int stride = area | 1;
+	const int mine = (lane & (nCopy - 1)) * stride;
+	for (int t = threadIdx.x; t < nCopy * stride; t += kThreads) cnt[t] = 0u;
+	__syncthreads();
+#pragma unroll
+	for (int k = 0; k < kPhItems; k++)
+		if ((in >> k) & 1u) atomicAdd(&cnt[mine + (NA > 1 ? (bin[NA - 1][k] - lo1) * w0 : 0) + (bin[0][k] - lo0)], 1u);
+	__syncthreads();
+	for (int t = threadIdx.x; t < area; t += kThreads) {
+		unsigned v = cnt[t];
+		for (int c = 1; c < nCopy; c++) v += cnt[c * stride + t];
+		if (!v) continue;
+		const int r1 = t / w0, r0 = t - r1 * w0;
+		atomicAdd(&hist[(lo1 + r1) * nb0 + lo0 + r0], (unsigned long long)v);
 	}
 }
 
@@ -3151,6 +3306,36 @@ extern "C" int pinc_hip_moments(pinc_pop_t pop, int s, pinc_geom_t g, const doub
 	else
 		hipLaunchKernelGGL((k_moments<1>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
 	return check_launch("moments");
+}
+
+extern "C" long pinc_hip_phase_lds_bins(void) { return kPhLds; }
+
+extern "C" int pinc_hip_phase_hist(pinc_pop_t pop, int s, const double *const v[3], pinc_phase_t spec,
+                                   unsigned long long *hist, unsigned long long *outside, void *stream) {
+	if (pop.nd < 1 || pop.nd > 3 || s < 0 || s >= PINC_MAX_SPECIES || !v || !hist || !outside)
+		return set_error(hipErrorInvalidValue, "phase_hist: bad species, dimensions or null array");
+	const int na = spec.axis[1] == PINC_PS_NONE ? 1 : 2;
+	const double *c[2] = {nullptr, nullptr};
+	for (int a = 0; a < na; a++) {
+		const int ax = spec.axis[a];
+		if (ax < PINC_PS_X || ax > PINC_PS_VZ) return set_error(hipErrorInvalidValue, "phase_hist: axis is no PINC_PS_*");
+		if (ax % 3 >= pop.nd) return set_error(hipErrorInvalidValue, "phase_hist: axis beyond the population's dimensions");
+		c[a] = ax < PINC_PS_VX ? pop.x[ax] : v[ax - PINC_PS_VX];
+		if (!c[a]) return set_error(hipErrorInvalidValue, "phase_hist: null particle array");
+		if (spec.nbins[a] < 1) return set_error(hipErrorInvalidValue, "phase_hist: nbins < 1");
+	}
+	if (na == 1 && spec.nbins[1] != 1) return set_error(hipErrorInvalidValue, "phase_hist: nbins[1] != 1 without a second axis");
+	if ((long)spec.nbins[0] * spec.nbins[1] > (1L << 24))
+		return set_error(hipErrorInvalidValue, "phase_hist: more than 2^24 bins");
+	const long b0 = pop.iStart[s], n = pop.iStop[s] - b0;
+	if (n <= 0) return 0;
+	const long nb = ceil_div(n + (b0 & 1L), (long)kPhChunk);
+	hipStream_t st = (hipStream_t)stream;
+	if (na == 1)
+		hipLaunchKernelGGL((k_phase_hist<1>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], b0, n, spec, hist, outside);
+	else
+		hipLaunchKernelGGL((k_phase_hist<2>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], b0, n, spec, hist, outside);
+	return check_launch("phase_hist");
 }
 
 extern "C" int pinc_hip_field_chain_all(const double *E, double *Es, long n, const double *qm, const double *mq,

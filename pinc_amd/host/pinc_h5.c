@@ -434,6 +434,37 @@ void xyCloseH5(long long h5) {
 	if (h5 > 0) H.Fclose(h5);
 }
 
+/* -------------------------------------------------------- phase space -- */
+
+/* <files:output>_<fName>.ps.h5 (not in the reference): file attributes
+ * "axes" (PINC_PS_* codes), "min" and "max", one value per axis */
+long long psOpenH5(const dictionary *ini, const char *fName, const PhaseSpec *spec) {
+	hid_t f = open_file(ini, fName, "ps");
+	const int na = spec->axis[1] == PINC_PS_NONE ? 1 : 2;
+	const double axes[2] = {spec->axis[0], spec->axis[1]};
+	set_attr(f, "axes", axes, na);
+	set_attr(f, "min", spec->lo, na);
+	set_attr(f, "max", spec->hi, na);
+	return f;
+}
+
+/* dataset "/n=%.1f" of shape [nbins1, nbins0] with the attribute "outside";
+ * hist is the global histogram (puPhaseHist), rank 0 writes */
+void psWriteH5(long long h5, const PhaseSpec *spec, const double *hist, double outside, double n) {
+	if (g_pinc.rank != 0 || h5 < 0) return;
+	const int na = spec->axis[1] == PINC_PS_NONE ? 1 : 2;
+	hsize_t dims[2] = {(hsize_t)(na > 1 ? spec->nbins[1] : 1), (hsize_t)spec->nbins[0]};
+	char name[64];
+	snprintf(name, sizeof(name), "/n=%.1f", n);
+	write_dataset(h5, name, 2, dims, hist);
+	hid_t d = H.Dopen2(h5, name, H5P_DEFAULT);
+	h5ok(d, name);
+	if (H.Aexists(d, "outside") <= 0) set_attr(d, "outside", &outside, 1);
+	H.Dclose(d);
+}
+
+void psCloseH5(long long h5) { xyCloseH5(h5); }
+
 void pCreateEnergyDatasets(long long xy, Population *pop) {
 	char name[64];
 	xyCreateDataset(xy, "/energy/potential/total");

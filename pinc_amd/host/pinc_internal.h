@@ -174,6 +174,10 @@ struct PincDevPop {
 	/* multi-rank migration buffers (AoS records: nd pos, nd vel, ne) */
 	double *sendBuf[2], *recvBuf[2];
 	long sendCap, recvCap;
+	/* puPhaseHist's device counters (phaseBins of them and the outside count),
+	 * kept from call to call while the number of bins stays the same */
+	unsigned long long *phaseHist;
+	long phaseBins;
 };
 
 struct PincDevGrid {
@@ -355,6 +359,9 @@ void pinc_pop_flush_host(const Population *pop);
 /* kicked velocities pending after a sorting push, in the current order */
 void pinc_pot_energy_launch(const Grid *rho, const Grid *phi);
 void pinc_pending_vel(const Population *pop, int s, double *const *dst);
+/* what is wrong with a phase-space histogram's spec for nd dimensions (a bad
+ * axis, max <= min, no bins or more than 2^24), or NULL */
+const char *pinc_phase_spec_error(const PhaseSpec *spec, int nd);
 void pinc_literal_second_fold(const Population *pop, Grid *rho, int order);
 
 /* helpers shared by the host translation units */

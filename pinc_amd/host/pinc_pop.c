@@ -252,6 +252,7 @@ void pFree(Population *p) {
 			pinc_hip_free(dv->sendBuf[k]);
 			pinc_hip_free(dv->recvBuf[k]);
 		}
+		pinc_hip_free(dv->phaseHist);
 		free(dv);
 	}
 	free(p->pos);

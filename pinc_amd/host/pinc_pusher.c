@@ -1103,20 +1103,54 @@ void pinc_literal_second_fold(const Population *pop, Grid *rho, int order) {
 	pinc_check(pinc_hip_add(g->d, g->lit, g->n, g_pinc.stream), "second fold add");
 }
 
-/* ------------------------------------------------------------- moments -- */
+/* ---------------------------------------------- moments, phase space -- */
+/* The velocity arrays of species s's observable state, as pSyncToHost defines
+ * it (x_n in p.x, v_{n+1/2}), indexed like p.v.  With a fused push pending
+ * the kicked velocities are read where they already are: p.v (a push in
+ * place, or a sorting push whose kick was materialised), altV (a species the
+ * sorting push left in order), or a temporary filled by pinc_pending_vel (a
+ * species whose sorting push is pending).  No state of the schedule changes.
+ * Returns the temporary (or NULL) for observable_vel_done, after the kernels
+ * that read v were launched. */
+static double *observable_vel(Population *pop, int s, const double *v[3], const char *what) {
+	PincDevPop *dv = pop->dev;
+	const int nd = pop->nDims;
+	const long a = pop->iStart[s], n = pop->iStop[s] - a;
+	pinc_pop_t p = pinc_devpop(pop);
+	for (int d = 0; d < 3; d++) v[d] = p.v[d];
+	double *tmp = NULL;
+	if (n > 0 && dv->pending && dv->pendingSorted) {
+		if (dv->permId[s]) {
+			for (int d = 0; d < nd; d++) v[d] = dv->altV[d];
+		} else if (!dv->vKicked[s]) {
+			/* (n + 2 per component, the first at an index of a's parity: the
+			 * kernel's 16-byte loads stay aligned) */
+			const long pitch = (n + 3) & ~1L;
+			pinc_check(pinc_hip_malloc((void **)&tmp, nd * pitch * sizeof(double)), what);
+			double *dst[3] = {NULL, NULL, NULL};
+			for (int d = 0; d < nd; d++) {
+				dst[d] = tmp + d * pitch + (a & 1L);
+				v[d] = dst[d] - a;
+			}
+			pinc_pending_vel(pop, s, dst);
+		}
+	}
+	return tmp;
+}
+
+static void observable_vel_done(double *tmp, const char *what) {
+	if (!tmp) return;
+	pinc_check(pinc_hip_stream_sync(g_pinc.stream), what);
+	pinc_hip_free(tmp);
+}
+
 /* The first velocity moments of species s on the grid (pinc_hip_moments; an
  * extension, not in the reference): mom = 0, then the deposit of the
- * observable state, as pSyncToHost defines it.  With a fused push pending
- * that is the pre-move positions (p.x) and the kicked velocities, read where
- * they already are: p.v (a push in place, or a sorting push whose kick was
- * materialised), altV (a species the sorting push left in order), or a
- * temporary filled by pinc_pending_vel (a species whose sorting push is
- * pending).  No state of the schedule changes.  Ghost contributions are left
+ * observable state (observable_vel).  Ghost contributions are left
  * unfolded, as puDistr leaves them: gHaloOp(addSlice, mom, mpiInfo, FROMHALO)
  * folds them.  mom never takes part in the literal second fold. */
 void puMomentsND1(Population *pop, int s, Grid *mom) {
 	pinc_pop_flush_host(pop);
-	PincDevPop *dv = pop->dev;
 	PincDevGrid *g = mom->dev;
 	const int nd = pop->nDims, nm = 1 + nd + nd * (nd + 1) / 2;
 	if (s < 0 || s >= pop->nSpecies) msg(ERROR, "puMomentsND1: species %d out of range", s);
@@ -1127,34 +1161,84 @@ void puMomentsND1(Population *pop, int s, Grid *mom) {
 	g->ghostsValid = 0;
 	g->depPop = NULL;
 	g->folds = 0;
-	const long a = pop->iStart[s], n = pop->iStop[s] - a;
-	if (n <= 0) return;
-	pinc_pop_t p = pinc_devpop(pop);
-	const double *v[3] = {p.v[0], p.v[1], p.v[2]};
-	double *tmp = NULL;
-	if (dv->pending && dv->pendingSorted) {
-		if (dv->permId[s]) {
-			for (int d = 0; d < nd; d++) v[d] = dv->altV[d];
-		} else if (!dv->vKicked[s]) {
-			/* (n + 2 per component, the first at an index of a's parity: the
-			 * kernel's 16-byte loads stay aligned) */
-			const long pitch = (n + 3) & ~1L;
-			pinc_check(pinc_hip_malloc((void **)&tmp, nd * pitch * sizeof(double)), "moments velocities");
-			double *dst[3] = {NULL, NULL, NULL};
-			for (int d = 0; d < nd; d++) {
-				dst[d] = tmp + d * pitch + (a & 1L);
-				v[d] = dst[d] - a;
-			}
-			pinc_pending_vel(pop, s, dst);
-		}
-	}
+	if (pop->iStop[s] - pop->iStart[s] <= 0) return;
+	const double *v[3];
+	double *tmp = observable_vel(pop, s, v, "moments velocities");
 	pinc_geom_t geo = g->geom;
 	geo.literal = 0;
-	pinc_check(pinc_hip_moments(p, s, geo, v, g->d, g_pinc.stream), "moments");
-	if (tmp) {
-		pinc_check(pinc_hip_stream_sync(g_pinc.stream), "moments");
-		pinc_hip_free(tmp);
+	pinc_check(pinc_hip_moments(pinc_devpop(pop), s, geo, v, g->d, g_pinc.stream), "moments");
+	observable_vel_done(tmp, "moments");
+}
+
+/* what is wrong with a histogram's spec for nd dimensions, or NULL */
+const char *pinc_phase_spec_error(const PhaseSpec *spec, int nd) {
+	const int na = spec->axis[1] == PINC_PS_NONE ? 1 : 2;
+	long nb = 1;
+	for (int a = 0; a < na; a++) {
+		const int ax = spec->axis[a];
+		if (ax < PINC_PS_X || ax > PINC_PS_VZ) return "an axis is none of x y z vx vy vz";
+		if (ax % 3 >= nd) return "an axis beyond the population's dimensions";
+		if (spec->nbins[a] < 1) return "fewer than one bin";
+		if (!(spec->hi[a] > spec->lo[a])) return "max must be above min";
+		if (!isfinite(spec->hi[a] - spec->lo[a])) return "range not finite";
+		nb *= spec->nbins[a];
+		if (nb > (1L << 24)) return "more than 2^24 bins";
 	}
+	return NULL;
+}
+
+/* Phase-space histogram of species s (pinc_hip_phase_hist; an extension, not
+ * in the reference) over the observable state (observable_vel): positions in
+ * the global frame (local + mpiInfo->offset, the addition pWriteH5 makes),
+ * velocities in code units.  The device histogram (cached per size in the
+ * device population) is cleared and filled, read back, converted to double
+ * and summed over the ranks: every rank gets the global histogram, the call
+ * is collective.  Counts below 2^53 are exact in fp64, and so is the sum. */
+void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *mpiInfo, double *hist, double *outside) {
+	pinc_pop_flush_host(pop);
+	PincDevPop *dv = pop->dev;
+	const int nd = pop->nDims;
+	if (s < 0 || s >= pop->nSpecies) msg(ERROR, "puPhaseHist: species %d out of range", s);
+	const int na = spec->axis[1] == PINC_PS_NONE ? 1 : 2;
+	pinc_phase_t ps = {{spec->axis[0], na > 1 ? spec->axis[1] : PINC_PS_NONE}, {spec->nbins[0], 1}, {0, 0}, {0, 0}, {1, 1}};
+	const char *bad = pinc_phase_spec_error(spec, nd);
+	if (bad) msg(ERROR, "puPhaseHist: %s", bad);
+	for (int a = 0; a < na; a++) {
+		const int ax = spec->axis[a];
+		ps.nbins[a] = spec->nbins[a];
+		ps.shift[a] = ax < PINC_PS_VX ? (double)mpiInfo->offset[ax] : 0.;
+		ps.lo[a] = spec->lo[a];
+		ps.scale[a] = spec->nbins[a] / (spec->hi[a] - spec->lo[a]);
+	}
+	const long nb = (long)ps.nbins[0] * ps.nbins[1];
+	/* the counters and, behind them, the outside count */
+	if (dv->phaseBins != nb) {
+		pinc_hip_free(dv->phaseHist);
+		dv->phaseHist = NULL;
+		pinc_check(pinc_hip_malloc((void **)&dv->phaseHist, (nb + 1) * sizeof(unsigned long long)), "phase histogram");
+		dv->phaseBins = nb;
+	}
+	unsigned long long *d = dv->phaseHist;
+	pinc_check(pinc_hip_memset(d, 0, (nb + 1) * sizeof(unsigned long long), g_pinc.stream), "phase histogram zero");
+	const double *v[3];
+	double *tmp = observable_vel(pop, s, v, "phase velocities");
+	pinc_check(pinc_hip_phase_hist(pinc_devpop(pop), s, v, ps, d, d + nb, g_pinc.stream), "phase histogram");
+	observable_vel_done(tmp, "phase histogram");
+	unsigned long long *h = malloc((nb + 1) * sizeof(unsigned long long));
+	pinc_check(pinc_hip_d2h(h, d, (nb + 1) * sizeof(unsigned long long), g_pinc.stream), "phase histogram");
+	double *sum = malloc((nb + 1) * sizeof(double));
+	for (long i = 0; i <= nb; i++) sum[i] = (double)h[i];
+	free(h);
+	if (g_pinc.nranks > 1) {
+		/* (pinc_comm_allreduce_sum works on device memory: the counters'
+		 * buffer, 8 bytes each as well, carries the doubles) */
+		pinc_check(pinc_hip_h2d(d, sum, (nb + 1) * sizeof(double), g_pinc.stream), "phase histogram");
+		pinc_comm_allreduce_sum((double *)d, nb + 1, "phase histogram");
+		pinc_check(pinc_hip_d2h(sum, d, (nb + 1) * sizeof(double), g_pinc.stream), "phase histogram");
+	}
+	memcpy(hist, sum, nb * sizeof(double));
+	*outside = sum[nb];
+	free(sum);
 }
 
 void puDistr3D1(const Population *pop, Grid *rho) { distr(pop, rho); }

@@ -60,6 +60,14 @@ struct PincSim {
 	Grid *mom[PINC_MAX_SPECIES];
 	int momEvery;      /* diagnostics:moments = N: written every N-th step (0: off) */
 	int momOutput;     /* their files are open */
+	/* phase-space histograms (puPhaseHist) of the ini's spec, allocated when
+	 * diagnostics:phaseSpace > 0 */
+	PhaseSpec phase;
+	int phaseEvery;    /* diagnostics:phaseSpace = N: written every N-th step (0: off) */
+	double *phaseHist; /* host, the last histogram taken */
+	double phaseOutside;
+	long long phaseFile[PINC_MAX_SPECIES];
+	int phaseOutput;   /* their files are open */
 };
 
 static int g_simActive = 0;
@@ -124,6 +132,68 @@ static void mom_free(PincSim *S) {
 	S->momOutput = 0;
 }
 
+/* -------------------------------------------------------- phase space -- */
+/* diagnostics:phaseSpace = N with phaseSpaceAxes, phaseSpaceBins,
+ * phaseSpaceMin and phaseSpaceMax (one or two entries each) */
+static void phase_read_ini(PincSim *S) {
+	const dictionary *ini = S->ini;
+	S->phaseEvery = iniHas(ini, "diagnostics:phaseSpace") ? iniGetInt(ini, "diagnostics:phaseSpace") : 0;
+	if (S->phaseEvery < 0) msg(ERROR, "diagnostics:phaseSpace must be >= 0");
+	if (S->phaseEvery == 0) return;
+	static const char *const names[6] = {"x", "y", "z", "vx", "vy", "vz"};
+	const int na = iniGetNElements(ini, "diagnostics:phaseSpaceAxes");
+	if (na < 1 || na > 2) msg(ERROR, "diagnostics:phaseSpaceAxes takes one or two of x y z vx vy vz");
+	char **axes = iniGetStrArr(ini, "diagnostics:phaseSpaceAxes", na);
+	int *bins = iniGetIntArr(ini, "diagnostics:phaseSpaceBins", na);
+	double *lo = iniGetDoubleArr(ini, "diagnostics:phaseSpaceMin", na);
+	double *hi = iniGetDoubleArr(ini, "diagnostics:phaseSpaceMax", na);
+	PhaseSpec *p = &S->phase;
+	p->axis[1] = PINC_PS_NONE;
+	p->nbins[1] = 1;
+	for (int a = 0; a < na; a++) {
+		p->axis[a] = PINC_PS_VZ + 1;
+		for (int k = 0; k < 6; k++)
+			if (!strcmp(axes[a], names[k])) p->axis[a] = k;
+		p->nbins[a] = bins[a];
+		p->lo[a] = lo[a];
+		p->hi[a] = hi[a];
+	}
+	const char *bad = pinc_phase_spec_error(p, S->pop->nDims);
+	if (bad) msg(ERROR, "diagnostics:phaseSpace: %s", bad);
+	freeStrArr(axes);
+	free(bins);
+	free(lo);
+	free(hi);
+	S->phaseHist = malloc((long)p->nbins[0] * p->nbins[1] * sizeof(double));
+}
+
+/* species s's histogram of the ini's spec in S->phaseHist, S->phaseOutside */
+static void phase_compute(PincSim *S, int s) {
+	puPhaseHist(S->pop, s, &S->phase, S->mpi, S->phaseHist, &S->phaseOutside);
+}
+
+static void phase_write(PincSim *S, double n) {
+	if (S->phaseEvery <= 0 || (long)n % S->phaseEvery != 0) return;
+	for (int s = 0; s < S->pop->nSpecies; s++) {
+		if (!S->phaseOutput) {
+			char name[32];
+			snprintf(name, sizeof(name), "phase%d", s);
+			S->phaseFile[s] = psOpenH5(S->ini, name, &S->phase);
+		}
+		phase_compute(S, s);
+		psWriteH5(S->phaseFile[s], &S->phase, S->phaseHist, S->phaseOutside, n);
+	}
+	S->phaseOutput = 1;
+}
+
+static void phase_free(PincSim *S) {
+	if (S->phaseOutput)
+		for (int s = 0; s < S->pop->nSpecies; s++) psCloseH5(S->phaseFile[s]);
+	S->phaseOutput = 0;
+	free(S->phaseHist);
+	S->phaseHist = NULL;
+}
+
 static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
 	PincSim *S = calloc(1, sizeof(*S));
 	S->ini = ini;
@@ -186,6 +256,7 @@ static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
 	S->momEvery = iniHas(ini, "diagnostics:moments") ? iniGetInt(ini, "diagnostics:moments") : 0;
 	if (S->momEvery < 0) msg(ERROR, "diagnostics:moments must be >= 0");
 	if (S->momEvery > 0) mom_alloc(S);
+	phase_read_ini(S);
 	return S;
 }
 
@@ -317,12 +388,14 @@ static void output_write(PincSim *S, double n) {
 	pWriteH5(S->pop, S->mpi, n, n + 0.5);
 	pWriteEnergy(S->history, S->pop, n);
 	mom_write(S, n);
+	phase_write(S, n);
 }
 
 static void sim_free(PincSim *S) {
 	if (!S) return;
 	output_close(S);
 	mom_free(S);
+	phase_free(S);
 	pinc_obj_free(S->obj);
 	if (S->solverFree) S->solverFree(S->solver);
 	gFree(S->E);
@@ -354,7 +427,10 @@ void regular(dictionary *ini) {
 		pinc_sim_energy(S, &ke, &pe, NULL);
 		msg(STATUS, "KE %.17g PE %.17g", ke, pe);
 		if (h5) output_write(S, (double)n);
-		else mom_write(S, (double)n);
+		else {
+			mom_write(S, (double)n);
+			phase_write(S, (double)n);
+		}
 	}
 	S->ini = NULL; /* owned by the caller */
 	sim_free(S);
@@ -426,6 +502,12 @@ int pinc_sim_op(PincSim *S, const char *op) {
 		gPotEnergy(S->rho, S->phi, S->pop);
 	} else if (!strcmp(op, "moments")) {
 		for (int s = 0; s < S->pop->nSpecies; s++) mom_compute(S, s);
+	} else if (!strcmp(op, "phase")) {
+		if (S->phaseEvery <= 0) {
+			msg(WARNING, "op phase without diagnostics:phaseSpace");
+			return 1;
+		}
+		for (int s = 0; s < S->pop->nSpecies; s++) phase_compute(S, s);
 	} else if (!strcmp(op, "step")) sim_step(S);
 	else {
 		msg(WARNING, "unknown op %s", op);
@@ -568,6 +650,25 @@ int pinc_sim_moments(PincSim *S, int s, double *out) {
 				const long node = (i + G[0]) + (long)Sz[0] * ((j + G[1]) + (long)Sz[1] * (k + G[2]));
 				for (int v = 0; v < nv; v++) out[o++] = g->val[node * nv + v];
 			}
+	return 0;
+}
+
+int pinc_sim_phase_hist(PincSim *S, int s, const PhaseSpec *spec, double *hist, double *outside) {
+	if (s < 0 || s >= S->pop->nSpecies) {
+		msg(WARNING, "pinc_sim_phase_hist: species %d out of range", s);
+		return 1;
+	}
+	const char *bad = pinc_phase_spec_error(spec, S->pop->nDims);
+	if (bad) {
+		msg(WARNING, "pinc_sim_phase_hist: %s", bad);
+		return 1;
+	}
+	puPhaseHist(S->pop, s, spec, S->mpi, hist, outside);
+	return 0;
+}
+
+int pinc_sim_offset(PincSim *S, int *offset) {
+	for (int d = 0; d < S->pop->nDims; d++) offset[d] = S->mpi->offset[d];
 	return 0;
 }
 

@@ -185,6 +185,40 @@ class Sim:
             raise ValueError(f"moments: no species {s}")
         return out.reshape(tuple(reversed(size[1:1 + self.ndims])) + (size[0],))
 
+    def phase_space(self, s: int, axes=("x", "vx"), bins=(64, 64), lo=(0.0, -1.0), hi=(1.0, 1.0)):
+        """Histogram of species s over one or two of x y z vx vy vz at
+        (x_n, v_n+1/2): bins[a] equal bins over [lo[a], hi[a]), positions in
+        the global frame (particles() + offset), velocities in code units;
+        the binning rule is pinc_hip_phase_hist's.  Returns (hist,
+        outside): float64 counts of shape [bins[1], bins[0]] ([bins[0]] for
+        one axis), summed over the ranks (the call is collective), and the
+        number of particles outside the range."""
+        from .phase import AXES
+        axes = (axes,) if isinstance(axes, str) else tuple(axes)
+        bins, lo, hi = (tuple(np.atleast_1d(a).tolist()) for a in (bins, lo, hi))
+        na = len(axes)
+        if na not in (1, 2) or any(a not in AXES for a in axes) or not (len(bins) == len(lo) == len(hi) == na):
+            raise ValueError(f"phase_space: axes {axes} with bins {bins}, lo {lo}, hi {hi}")
+        if any(int(b) != b or b < 1 for b in bins) or int(np.prod(bins)) > 1 << 24:
+            raise ValueError(f"phase_space: bins {bins}")
+        spec = _lib.PhaseSpec()
+        spec.axis[1], spec.nbins[1] = -1, 1
+        for a in range(na):
+            spec.axis[a], spec.nbins[a], spec.lo[a], spec.hi[a] = AXES.index(axes[a]), int(bins[a]), lo[a], hi[a]
+        out = np.zeros(tuple(int(b) for b in reversed(bins)))
+        outside = C.c_double()
+        if HOST.pinc_sim_phase_hist(self._h, s, C.byref(spec), out.ctypes.data, C.byref(outside)):
+            raise ValueError(f"phase_space: bad species {s} or spec (axes {axes}, bins {bins}, lo {lo}, hi {hi})")
+        return out, outside.value
+
+    @property
+    def offset(self) -> np.ndarray:
+        """This rank's offset of the local frame (particles()) to the global
+        one, per dimension."""
+        off = (C.c_int * 3)()
+        HOST.pinc_sim_offset(self._h, off)
+        return np.array(off[:self.ndims], dtype=np.int64)
+
     def emigrants(self) -> np.ndarray:
         n = 3 ** self.ndims * self.nspecies
         out = np.zeros(n, dtype=np.int64)
