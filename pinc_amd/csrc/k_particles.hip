@@ -371,15 +371,29 @@ __device__ __forceinline__ long node_off(const Geo &G, int d, int p) {
 }
 
 // --------------------------------------------- LDS-privatised deposit -----
-// One workgroup owns a chunk of kDepChunk consecutive particles; each thread
-// owns kDepItems consecutive ones (loaded 16 B at a time).  In either layout
-// (the reference's order, spatially coherent from the lattice start, or the
-// cell-sorted tiled layout) consecutive particles mostly share a cell and a
-// chunk covers a small box of nodes:
+// The frame shared by the kernels that scatter a species through an LDS box
+// owned by the workgroup (k_deposit_tiled, k_moments, k_phase_hist; the box
+// also k_deposit_cells), each piece written once below:
+//  * ChunkItems: a workgroup owns a chunk of kThreads * ITEMS consecutive
+//    particles, a thread ITEMS consecutive ones, loaded 16 B at a time from
+//    the 16-byte aligned slot at or below iStart; the guards of an odd iStart
+//    and of the partial last chunk are load2() and live();
+//  * BlockBounds: the block's minimum, maximum (and sum) of per-thread integer
+//    bounds, and one more count, through DPP wave reductions and LDS.  Which
+//    box follows from them is each kernel's policy;
+//  * NodeBox: a box of grid nodes in LDS: zero(), the index of a cell whose
+//    upper neighbours are inside too, the corners' offsets, and the flush with
+//    one global atomic per value that is not zero;
+//  * cell_split: a particle's cell, the fractions of its CIC weights, and
+//    whether it continues the thread's run of particles in one cell.
+//
+// k_deposit_tiled: in either layout (the reference's order, spatially
+// coherent from the lattice start, or the cell-sorted tiled layout)
+// consecutive particles mostly share a cell and a chunk covers a small box of
+// nodes:
 //  * a thread sums the eight weights of a run of particles in one cell in
 //    registers and adds them once (cell-sorted: once per kDepItems);
-//  * the box is accumulated in LDS (ds_add_f64) and flushed with one global
-//    atomic per touched node.
+//  * the chunk's bounding box is accumulated in LDS (ds_add_f64) and flushed.
 // Chunks whose box exceeds the LDS tile use the same run accumulation with
 // global atomics.  Weights are the reference's expressions (pusher.c:550-565,
 // 626-638); only the summation order differs from the serial loop.
@@ -507,6 +521,186 @@ __device__ __forceinline__ long corner_off(const Geo &G, const int *j, int c) {
 	return off;
 }
 
+constexpr int kWaves = kThreads / 64;
+
+// A thread's ITEMS consecutive particles of its workgroup's chunk: slots i0 ..
+// i0 + ITEMS - 1 of the species [b0, end), i0 even relative to the 16-byte
+// aligned slot at or below b0.
+template <int ITEMS>
+struct ChunkItems {
+	long i0, b0, end;
+	unsigned valid;  // bit k: slot i0 + k is a particle of the species
+	__device__ __forceinline__ ChunkItems(long first, long n) : b0(first), end(first + n) {
+		i0 = (b0 & ~1L) + (long)blockIdx.x * (kThreads * ITEMS) + (long)threadIdx.x * ITEMS;
+		valid = 0;
+#pragma unroll
+		for (int k = 0; k < ITEMS; k++) valid |= (unsigned)(i0 + k >= b0 && i0 + k < end) << k;
+	}
+	__device__ __forceinline__ bool live(int k) const { return (valid >> k) & 1u; }
+	// p[i0 + k], p[i0 + k + 1] (k even): one 16-byte load where both are live,
+	// else each on its own, 0 for a slot that is not
+	__device__ __forceinline__ void load2(const double *p, int k, double &a, double &b) const {
+		long i = i0 + k;
+		if (i >= b0 && i + 1 < end) {
+			double2 v = *reinterpret_cast<const double2 *>(p + i);
+			a = v.x;
+			b = v.y;
+		} else {
+			a = (i >= b0 && i < end) ? p[i] : 0.0;
+			b = (i + 1 >= b0 && i + 1 < end) ? p[i + 1] : 0.0;
+		}
+	}
+};
+// workgroups of a species [b0, b0 + n) in chunks of `chunk` particles
+inline long chunk_blocks(long b0, long n, long chunk) { return (n + (b0 & 1L) + chunk - 1) / chunk; }
+
+// cell of a coordinate; CLAMP keeps it inside the slab (0..T)
+template <bool CLAMP>
+__device__ __forceinline__ int cell_of(double x, int T) {
+	return CLAMP ? min(max((int)x, 0), T) : (int)x;
+}
+
+// A particle's cell j, its fractions dec and comp = 1 - dec of the CIC
+// weights, and whether j is the cell cj of the thread's current run.
+template <int ND, bool CLAMP>
+__device__ __forceinline__ bool cell_split(const double *x, const int *T, const int *cj, int *j, double *dec,
+                                           double *comp) {
+	bool same = true;
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+		j[d] = cell_of<CLAMP>(x[d], T[d]);
+		dec[d] = x[d] - j[d];
+		comp[d] = 1 - dec[d];
+		same = same && (j[d] == cj[d]);
+	}
+	return same;
+}
+
+// lo, hi (the upper node, cell + 1) and sum of the cells of a thread's live
+// particles along one dimension (p: that coordinate's array)
+template <bool CLAMP, int ITEMS>
+__device__ __forceinline__ void chunk_cell_bounds(const ChunkItems<ITEMS> &ch, const double *p, int T, int &lo,
+                                                  int &hi, int &sum) {
+#pragma unroll
+	for (int k = 0; k < ITEMS; k += 2) {
+		double x[2];
+		ch.load2(p, k, x[0], x[1]);
+#pragma unroll
+		for (int h = 0; h < 2; h++)
+			if (ch.live(k + h)) {
+				const int c = cell_of<CLAMP>(x[h], T);
+				lo = min(lo, c);
+				hi = max(hi, c + 1);
+				sum += c;
+			}
+	}
+}
+
+// Block reduction of per-thread bounds (in LDS: __shared__): minimum of lo[d],
+// maximum of hi[d] and, with SUM, the sum of sum[d] for d < nd <= N, and with
+// EXTRA the sum of one more integer.  reduce() is called by every thread and
+// ends in a barrier; after it any thread reads the block's values with get()
+// and extra().
+template <int N, bool SUM, bool EXTRA>
+struct BlockBounds {
+	static constexpr int S = SUM ? 3 : 2;
+	int red[(S * N + (EXTRA ? 1 : 0)) * kWaves];
+	__device__ __forceinline__ void reduce(int nd, const int *lo, const int *hi, const int *sum, int extra) {
+		const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+		for (int d = 0; d < nd; d++) {
+			const int a = wave_min_i(lo[d]), b = wave_max_i(hi[d]);
+			int c = 0;
+			if constexpr (SUM) c = wave_sum_i(sum[d]);
+			if (lane == 0) {
+				red[(S * d) * kWaves + wv] = a;
+				red[(S * d + 1) * kWaves + wv] = b;
+				if constexpr (SUM) red[(S * d + 2) * kWaves + wv] = c;
+			}
+		}
+		if constexpr (EXTRA) {
+			const int c = wave_sum_i(extra);
+			if (lane == 0) red[S * N * kWaves + wv] = c;
+		}
+		__syncthreads();
+	}
+	__device__ __forceinline__ void get(int d, int &lo, int &hi, int &sum) const {
+		lo = INT32_MAX, hi = INT32_MIN, sum = 0;
+		for (int w = 0; w < kWaves; w++) {
+			lo = min(lo, red[(S * d) * kWaves + w]);
+			hi = max(hi, red[(S * d + 1) * kWaves + w]);
+			if constexpr (SUM) sum += red[(S * d + 2) * kWaves + w];
+		}
+	}
+	__device__ __forceinline__ int extra() const {
+		static_assert(EXTRA, "no extra count in this layout");
+		int c = 0;
+		for (int w = 0; w < kWaves; w++) c += red[S * N * kWaves + w];
+		return c;
+	}
+};
+
+// A box of grid nodes lo[d] .. lo[d] + n[d] - 1 (padded node coordinates)
+// that a workgroup accumulates in LDS, perNode values per node, value-major;
+// vol = 0: no box.  Block-uniform.
+template <int ND>
+struct NodeBox {
+	int lo[3] = {0, 0, 0}, n[3] = {1, 1, 1}, st[3] = {0, 0, 0};
+	int vol = 0;
+	NodeBox() = default;
+	__device__ __forceinline__ NodeBox(const int *first, const int *extent) {
+		vol = 1;
+#pragma unroll
+		for (int d = 0; d < ND; d++) {
+			lo[d] = first[d];
+			n[d] = extent[d];
+			st[d] = vol;
+			vol *= n[d];
+		}
+	}
+	__device__ __forceinline__ void zero(double *acc, int perNode) const {
+		for (int t = threadIdx.x; t < vol * perNode; t += kThreads) acc[t] = 0.0;
+	}
+	// l0: the linear index of the lower node of `cell`; true if the cell's
+	// upper neighbours are inside the box too
+	__device__ __forceinline__ bool index(const int *cell, int &l0) const {
+		bool in = true;
+		l0 = 0;
+#pragma unroll
+		for (int d = 0; d < ND; d++) {
+			const int r = cell[d] - lo[d];
+			in = in && r >= 0 && r + 1 < n[d];
+			l0 += r * st[d];
+		}
+		return in;
+	}
+	// offset of corner c (bit d: the upper node along d) from a cell's index
+	__device__ __forceinline__ int corner(int c) const {
+		int off = 0;
+#pragma unroll
+		for (int d = 0; d < ND; d++) off += ((c >> d) & 1) ? st[d] : 0;
+		return off;
+	}
+	// after a barrier: one global atomic per value that is not zero, in
+	// storage order
+	__device__ __forceinline__ void flush(const double *acc, int perNode, const Geo &G, double *dst) const {
+		for (int t = threadIdx.x; t < vol * perNode; t += kThreads) {
+			const double v = acc[t];
+			if (v == 0.0) continue;
+			int r = t / perNode;
+			const int m = t - r * perNode;
+			long off = 0;
+#pragma unroll
+			for (int d = 0; d < ND; d++) {
+				int c = r % n[d];
+				r /= n[d];
+				off += node_off(G, d, lo[d] + c);
+			}
+			unsafeAtomicAdd(&dst[off * perNode + m], v);
+		}
+	}
+};
+
 template <int ND, bool V3D>
 __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__restrict__ x0,
                                                             const double *__restrict__ x1,
@@ -515,65 +709,22 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
                                                             double *__restrict__ rho) {
 	constexpr int NC = 1 << ND;
 	__shared__ double acc[kDepCap];
-	__shared__ int red[2 * 3 * (kThreads / 64)];
+	__shared__ BlockBounds<3, false, false> bounds;
 	__shared__ int box[7];
 	Geo G = make_geo(g);
 	const double *xs[3] = {x0, x1, x2};
-	const long end = b0 + n;
-	// thread's items: i0 .. i0+kDepItems-1, i0 even relative to the 16-B
-	// aligned base below b0
-	const long i0 = (b0 & ~1L) + (long)blockIdx.x * kDepChunk + (long)threadIdx.x * kDepItems;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	auto load2 = [&](int d, int k, double &a, double &b) {
-		long i = i0 + k;
-		if (i >= b0 && i + 1 < end) {
-			double2 v = *reinterpret_cast<const double2 *>(xs[d] + i);
-			a = v.x;
-			b = v.y;
-		} else {
-			a = (i >= b0 && i < end) ? xs[d][i] : 0.0;
-			b = (i + 1 >= b0 && i + 1 < end) ? xs[d][i + 1] : 0.0;
-		}
-	};
-	unsigned valid = 0;
-#pragma unroll
-	for (int k = 0; k < kDepItems; k++) valid |= (unsigned)(i0 + k >= b0 && i0 + k < end) << k;
+	const ChunkItems<kDepItems> ch(b0, n);
 
 	// pass 1: bounding box of the chunk's cells (j .. j+1 per dimension)
-	int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+	int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, unused = 0;
 #pragma unroll
-	for (int d = 0; d < ND; d++) {
-#pragma unroll
-		for (int k = 0; k < kDepItems; k += 2) {
-			double a, b;
-			load2(d, k, a, b);
-			if ((valid >> k) & 1u) {
-				lo[d] = min(lo[d], (int)a);
-				hi[d] = max(hi[d], (int)a + 1);
-			}
-			if ((valid >> (k + 1)) & 1u) {
-				lo[d] = min(lo[d], (int)b);
-				hi[d] = max(hi[d], (int)b + 1);
-			}
-		}
-	}
-#pragma unroll
-	for (int d = 0; d < ND; d++) {
-		int a = wave_min_i(lo[d]), b = wave_max_i(hi[d]);
-		if (lane == 0) {
-			red[(2 * d) * (kThreads / 64) + wv] = a;
-			red[(2 * d + 1) * (kThreads / 64) + wv] = b;
-		}
-	}
-	__syncthreads();
+	for (int d = 0; d < ND; d++) chunk_cell_bounds<false>(ch, xs[d], 0, lo[d], hi[d], unused);
+	bounds.reduce(ND, lo, hi, nullptr, 0);
 	if (threadIdx.x == 0) {
 		long vol = 1;
 		for (int d = 0; d < ND; d++) {
-			int a = INT32_MAX, b = INT32_MIN;
-			for (int w = 0; w < kThreads / 64; w++) {
-				a = min(a, red[(2 * d) * (kThreads / 64) + w]);
-				b = max(b, red[(2 * d + 1) * (kThreads / 64) + w]);
-			}
+			int a, b, s;
+			bounds.get(d, a, b, s);
 			box[d] = a;
 			box[3 + d] = b - a + 1;
 			vol *= (long)(b - a + 1);
@@ -581,27 +732,12 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
 		box[6] = (vol <= kDepCap && vol > 0) ? (int)vol : 0;
 	}
 	__syncthreads();
-	const int vol = box[6];
 
-	int blo[3] = {0, 0, 0}, st[3] = {0, 0, 0}, bn[3] = {1, 1, 1};
-	if (vol) {
-		int sz = 1;
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			blo[d] = box[d];
-			bn[d] = box[3 + d];
-			st[d] = sz;
-			sz *= bn[d];
-		}
-		for (int t = threadIdx.x; t < vol; t += kThreads) acc[t] = 0.0;
+	NodeBox<ND> nb;
+	if (box[6]) {
+		nb = NodeBox<ND>(box, box + 3);
+		nb.zero(acc, 1);
 		__syncthreads();
-	}
-	int coff[NC];
-#pragma unroll
-	for (int c = 0; c < NC; c++) {
-		coff[c] = 0;
-#pragma unroll
-		for (int d = 0; d < ND; d++) coff[c] += ((c >> d) & 1) ? st[d] : 0;
 	}
 
 	// pass 2: runs of equal cells summed in registers
@@ -611,12 +747,12 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
 	for (int c = 0; c < NC; c++) a[c] = 0.0;
 	auto flush = [&]() {
 		if (cj[0] == INT32_MIN) return;
-		if (vol) {
-			int l0 = 0;
+		if (nb.vol) {
+			// (the bounding box: every run is inside)
+			int l0;
+			nb.index(cj, l0);
 #pragma unroll
-			for (int d = 0; d < ND; d++) l0 += (cj[d] - blo[d]) * st[d];
-#pragma unroll
-			for (int c = 0; c < NC; c++) atomicAdd(&acc[l0 + coff[c]], a[c]);
+			for (int c = 0; c < NC; c++) atomicAdd(&acc[l0 + nb.corner(c)], a[c]);
 		} else {
 #pragma unroll
 			for (int c = 0; c < NC; c++) unsafeAtomicAdd(&rho[corner_off<ND>(G, cj, c)], a[c]);
@@ -624,22 +760,15 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
 	};
 #pragma unroll 2
 	for (int k = 0; k < kDepItems; k += 2) {
-		double pp[3][2];
+		double pp[2][3];
 #pragma unroll
-		for (int d = 0; d < ND; d++) load2(d, k, pp[d][0], pp[d][1]);
+		for (int d = 0; d < ND; d++) ch.load2(xs[d], k, pp[0][d], pp[1][d]);
 #pragma unroll
 		for (int h = 0; h < 2; h++) {
-			if (!((valid >> (k + h)) & 1u)) continue;
+			if (!ch.live(k + h)) continue;
 			double dec[3], comp[3], w[NC];
 			int j[3];
-			bool same = true;
-#pragma unroll
-			for (int d = 0; d < ND; d++) {
-				j[d] = (int)pp[d][h];
-				dec[d] = pp[d][h] - j[d];
-				comp[d] = 1 - dec[d];
-				same = same && (j[d] == cj[d]);
-			}
+			const bool same = cell_split<ND, false>(pp[h], G.T, cj, j, dec, comp);
 			cic_weights<ND, V3D>(dec, comp, w);
 			literal_ghost_weights<ND>(g, j, w);
 			if (same) {
@@ -655,30 +784,17 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
 		}
 	}
 	flush();
-	if (!vol) return;
+	if (!nb.vol) return;
 	__syncthreads();
-
-	// flush the tile: one global atomic per touched node
-	for (int t = threadIdx.x; t < vol; t += kThreads) {
-		double v = acc[t];
-		if (v == 0.0) continue;
-		int r = t;
-		long off = 0;
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			int c = r % bn[d];
-			r /= bn[d];
-			off += node_off(G, d, blo[d] + c);
-		}
-		unsafeAtomicAdd(&rho[off], v);
-	}
+	nb.flush(acc, 1, G, rho);
 }
 
 // ---------------------------------------------------------- moments -------
 // The first velocity moments of one species on the grid (not in the
 // reference; include/pinc_hip.h has the definitions): per node NM = 1 + nd +
 // nd (nd + 1) / 2 sums of CIC weight times 1, v_i, v_i v_j (i <= j), value-major.
-// The deposit's structure with three differences (DESIGN.md "Moments"):
+// The frame above (ChunkItems, BlockBounds, NodeBox, cell_split) with three
+// differences from k_deposit_tiled (DESIGN.md "Moments"):
 //  * a node is NM doubles, so the LDS box holds kMomLds / NM nodes (640 in
 //    3-D, 50 KiB: three workgroups per CU).  A chunk whose cells' bounding
 //    box fits uses it; otherwise the box is a fixed shape around the chunk's
@@ -690,8 +806,9 @@ __global__ __launch_bounds__(kThreads) void k_deposit_tiled(const double *__rest
 //    thread's particles, which are read again (from cache) in each pass: 80
 //    accumulators in one pass would not fit the register budget of two waves
 //    per SIMD;
-//  * the box is flushed value by value in storage order, so a wave's global
-//    atomics cover the contiguous NM values of neighbouring nodes.
+//  * the box is value-major (NodeBox with perNode = NM): its flush runs value
+//    by value in storage order, so a wave's global atomics cover the
+//    contiguous NM values of neighbouring nodes.
 // geom.literal is ignored.  Cells are clamped to the slab (0..T_d), so that a
 // particle outside the frame cannot be deposited outside the array.
 constexpr int kMomItems = 16;
@@ -711,80 +828,24 @@ __global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__
 	constexpr int CAP = kMomLds / NM;  // nodes of the LDS box
 	static_assert(NG <= 3, "moment passes");
 	__shared__ double acc[kMomLds];
-	__shared__ int red[3 * 3 * (kThreads / 64) + (kThreads / 64)];
+	__shared__ BlockBounds<3, true, true> bounds;
 	__shared__ int box[7];
 	Geo G = make_geo(g);
 	const double *xs[3] = {x0, x1, x2};
 	const double *vs[3] = {v0, v1, v2};
-	const long end = b0 + n;
-	const long i0 = (b0 & ~1L) + (long)blockIdx.x * kMomChunk + (long)threadIdx.x * kMomItems;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	constexpr int NW = kThreads / 64;
-	auto load2 = [&](const double *p, int k, double &a, double &b) {
-		long i = i0 + k;
-		if (i >= b0 && i + 1 < end) {
-			double2 v = *reinterpret_cast<const double2 *>(p + i);
-			a = v.x;
-			b = v.y;
-		} else {
-			a = (i >= b0 && i < end) ? p[i] : 0.0;
-			b = (i + 1 >= b0 && i + 1 < end) ? p[i + 1] : 0.0;
-		}
-	};
-	// cell of a position, kept inside the slab
-	auto cell_of = [&](int d, double x) { return min(max((int)x, 0), G.T[d]); };
-	unsigned valid = 0;
-#pragma unroll
-	for (int k = 0; k < kMomItems; k++) valid |= (unsigned)(i0 + k >= b0 && i0 + k < end) << k;
+	const ChunkItems<kMomItems> ch(b0, n);
 
 	// pass 0: bounding box and mean of the chunk's cells
 	int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, sum[3] = {0, 0, 0};
 #pragma unroll
-	for (int d = 0; d < ND; d++) {
-#pragma unroll
-		for (int k = 0; k < kMomItems; k += 2) {
-			double a, b;
-			load2(xs[d], k, a, b);
-			if ((valid >> k) & 1u) {
-				const int c = cell_of(d, a);
-				lo[d] = min(lo[d], c);
-				hi[d] = max(hi[d], c + 1);
-				sum[d] += c;
-			}
-			if ((valid >> (k + 1)) & 1u) {
-				const int c = cell_of(d, b);
-				lo[d] = min(lo[d], c);
-				hi[d] = max(hi[d], c + 1);
-				sum[d] += c;
-			}
-		}
-	}
-#pragma unroll
-	for (int d = 0; d < ND; d++) {
-		int a = wave_min_i(lo[d]), b = wave_max_i(hi[d]), c = wave_sum_i(sum[d]);
-		if (lane == 0) {
-			red[(3 * d) * NW + wv] = a;
-			red[(3 * d + 1) * NW + wv] = b;
-			red[(3 * d + 2) * NW + wv] = c;
-		}
-	}
-	{
-		int c = wave_sum_i(__popc(valid));
-		if (lane == 0) red[9 * NW + wv] = c;
-	}
-	__syncthreads();
+	for (int d = 0; d < ND; d++) chunk_cell_bounds<true>(ch, xs[d], G.T[d], lo[d], hi[d], sum[d]);
+	bounds.reduce(ND, lo, hi, sum, __popc(ch.valid));
 	if (threadIdx.x == 0) {
-		int cnt = 0;
-		for (int w = 0; w < NW; w++) cnt += red[9 * NW + w];
+		const int cnt = bounds.extra();
 		long vol = 1;
 		int a[3], b[3], m[3];
 		for (int d = 0; d < ND; d++) {
-			a[d] = INT32_MAX, b[d] = INT32_MIN, m[d] = 0;
-			for (int w = 0; w < NW; w++) {
-				a[d] = min(a[d], red[(3 * d) * NW + w]);
-				b[d] = max(b[d], red[(3 * d + 1) * NW + w]);
-				m[d] += red[(3 * d + 2) * NW + w];
-			}
+			bounds.get(d, a[d], b[d], m[d]);
 			vol *= (long)(b[d] - a[d] + 1);
 		}
 		if (cnt > 0 && vol > CAP) {
@@ -805,29 +866,11 @@ __global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__
 		box[6] = cnt > 0 ? (int)vol : 0;
 	}
 	__syncthreads();
-	const int vol = box[6];
-	if (!vol) return;  // (no live particle in this chunk)
+	if (!box[6]) return;  // (no live particle in this chunk)
 
-	int blo[3] = {0, 0, 0}, st[3] = {0, 0, 0}, bn[3] = {1, 1, 1};
-	{
-		int sz = 1;
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			blo[d] = box[d];
-			bn[d] = box[3 + d];
-			st[d] = sz;
-			sz *= bn[d];
-		}
-	}
-	for (int t = threadIdx.x; t < vol * NM; t += kThreads) acc[t] = 0.0;
+	const NodeBox<ND> nb(box, box + 3);
+	nb.zero(acc, NM);
 	__syncthreads();
-	int coff[NC];
-#pragma unroll
-	for (int c = 0; c < NC; c++) {
-		coff[c] = 0;
-#pragma unroll
-		for (int d = 0; d < ND; d++) coff[c] += ((c >> d) & 1) ? st[d] : 0;
-	}
 
 	// passes 1..NG: moments [gm * GM, gm * GM + GM) of runs of equal cells
 	auto pass = [&](auto gc) {
@@ -841,19 +884,12 @@ __global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__
 			for (int q = 0; q < MN; q++) a[c][q] = 0.0;
 		auto flush = [&]() {
 			if (cj[0] == INT32_MIN) return;
-			bool in = true;
-			int l0 = 0;
-#pragma unroll
-			for (int d = 0; d < ND; d++) {
-				const int r = cj[d] - blo[d];
-				in = in && r >= 0 && r + 1 < bn[d];
-				l0 += r * st[d];
-			}
-			if (in) {
+			int l0;
+			if (nb.index(cj, l0)) {
 #pragma unroll
 				for (int c = 0; c < NC; c++)
 #pragma unroll
-					for (int q = 0; q < MN; q++) atomicAdd(&acc[(l0 + coff[c]) * NM + M0 + q], a[c][q]);
+					for (int q = 0; q < MN; q++) atomicAdd(&acc[(l0 + nb.corner(c)) * NM + M0 + q], a[c][q]);
 			} else {
 #pragma unroll
 				for (int c = 0; c < NC; c++) {
@@ -865,25 +901,18 @@ __global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__
 		};
 #pragma unroll 2
 		for (int k = 0; k < kMomItems; k += 2) {
-			double pp[3][2], pv[3][2];
+			double pp[2][3], pv[3][2];
 #pragma unroll
 			for (int d = 0; d < ND; d++) {
-				load2(xs[d], k, pp[d][0], pp[d][1]);
-				load2(vs[d], k, pv[d][0], pv[d][1]);
+				ch.load2(xs[d], k, pp[0][d], pp[1][d]);
+				ch.load2(vs[d], k, pv[d][0], pv[d][1]);
 			}
 #pragma unroll
 			for (int h = 0; h < 2; h++) {
-				if (!((valid >> (k + h)) & 1u)) continue;
+				if (!ch.live(k + h)) continue;
 				double dec[3], comp[3], w[NC], f[NM];
 				int j[3];
-				bool same = true;
-#pragma unroll
-				for (int d = 0; d < ND; d++) {
-					j[d] = cell_of(d, pp[d][h]);
-					dec[d] = pp[d][h] - j[d];
-					comp[d] = 1 - dec[d];
-					same = same && (j[d] == cj[d]);
-				}
+				const bool same = cell_split<ND, true>(pp[h], G.T, cj, j, dec, comp);
 				cic_weights<ND, ND == 3>(dec, comp, w);
 				// 1, v_i, v_i v_j (i <= j, row-major upper triangle)
 				f[0] = 1.0;
@@ -917,29 +946,14 @@ __global__ __launch_bounds__(kThreads) void k_moments(const double *__restrict__
 	if constexpr (NG > 1) pass(std::integral_constant<int, 1>{});
 	if constexpr (NG > 2) pass(std::integral_constant<int, 2>{});
 	__syncthreads();
-
-	// flush the box: values in storage order, one global atomic per touched value
-	for (int t = threadIdx.x; t < vol * NM; t += kThreads) {
-		const double v = acc[t];
-		if (v == 0.0) continue;
-		int r = t / NM;
-		const int m = t - r * NM;
-		long off = 0;
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			int c = r % bn[d];
-			r /= bn[d];
-			off += node_off(G, d, blo[d] + c);
-		}
-		unsafeAtomicAdd(&mom[off * NM + m], v);
-	}
+	nb.flush(acc, NM, G, mom);
 }
 
 // ------------------------------------------------------ phase space -------
 // Histogram of one species over NA = 1 or 2 of its coordinates (not in the
-// reference; include/pinc_hip.h has the binning rule).  The deposit's frame:
-// a workgroup owns kPhChunk consecutive particles, a thread kPhItems of them,
-// loaded as 16-byte pairs from the one or two arrays the spec names.
+// reference; include/pinc_hip.h has the binning rule).  Of the frame above it
+// uses ChunkItems, on the one or two arrays the spec names, and BlockBounds;
+// its counters are bins, not nodes, so the box is its own.
 //  * pass 0 bins the thread's particles (the bins stay in registers) and
 //    finds the chunk's bounding box in bin space from the inside particles;
 //  * a box of at most kPhLds bins is counted in LDS with 32-bit counters (a
@@ -968,39 +982,23 @@ __global__ __launch_bounds__(kThreads) void k_phase_hist(const double *__restric
                                                          long b0, long n, pinc_phase_t sp,
                                                          unsigned long long *__restrict__ hist,
                                                          unsigned long long *__restrict__ outside) {
-	constexpr int NW = kThreads / 64;
 	__shared__ unsigned cnt[kPhLds + 1];
-	__shared__ int red[(2 * NA + 1) * NW];
+	__shared__ BlockBounds<NA, false, true> bounds;
 	__shared__ int box[6];
 	const double *cs[2] = {c0, c1};
-	const long end = b0 + n;
-	const long i0 = (b0 & ~1L) + (long)blockIdx.x * kPhChunk + (long)threadIdx.x * kPhItems;
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	auto load2 = [&](const double *p, int k, double &a, double &b) {
-		long i = i0 + k;
-		if (i >= b0 && i + 1 < end) {
-			double2 v = *reinterpret_cast<const double2 *>(p + i);
-			a = v.x;
-			b = v.y;
-		} else {
-			a = (i >= b0 && i < end) ? p[i] : 0.0;
-			b = (i + 1 >= b0 && i + 1 < end) ? p[i + 1] : 0.0;
-		}
-	};
-	unsigned valid = 0;
-#pragma unroll
-	for (int k = 0; k < kPhItems; k++) valid |= (unsigned)(i0 + k >= b0 && i0 + k < end) << k;
+	const ChunkItems<kPhItems> ch(b0, n);
+	const int lane = threadIdx.x & 63;
 
 	// pass 0: the bins, and the chunk's bounding box of the inside particles
 	int bin[NA][kPhItems];
-	unsigned in = valid;
+	unsigned in = ch.valid;
 #pragma unroll
 	for (int a = 0; a < NA; a++) {
 		const double shift = sp.shift[a], lo = sp.lo[a], scale = sp.scale[a], nb = (double)sp.nbins[a];
 #pragma unroll
 		for (int k = 0; k < kPhItems; k += 2) {
 			double c[2];
-			load2(cs[a], k, c[0], c[1]);
+			ch.load2(cs[a], k, c[0], c[1]);
 #pragma unroll
 			for (int h = 0; h < 2; h++) {
 				const double t = ((c[h] + shift) - lo) * scale;
@@ -1021,32 +1019,16 @@ __global__ __launch_bounds__(kThreads) void k_phase_hist(const double *__restric
 				hi[a] = max(hi[a], bin[a][k]);
 			}
 	}
-#pragma unroll
-	for (int a = 0; a < NA; a++) {
-		const int x = wave_min_i(lo[a]), y = wave_max_i(hi[a]);
-		if (lane == 0) {
-			red[(2 * a) * NW + wv] = x;
-			red[(2 * a + 1) * NW + wv] = y;
-		}
-	}
-	{
-		const int o = wave_sum_i(__popc(valid & ~in));
-		if (lane == 0) red[2 * NA * NW + wv] = o;
-	}
-	__syncthreads();
+	bounds.reduce(NA, lo, hi, nullptr, __popc(ch.valid & ~in));
 	if (threadIdx.x == 0) {
-		int out = 0;
-		for (int w = 0; w < NW; w++) out += red[2 * NA * NW + w];
+		const int out = bounds.extra();
 		if (out) atomicAdd(outside, (unsigned long long)out);
 		long area = 1;
 		bool any = true;
 		box[1] = 0, box[3] = 1;
 		for (int a = 0; a < NA; a++) {
-			int x = INT32_MAX, y = INT32_MIN;
-			for (int w = 0; w < NW; w++) {
-				x = min(x, red[(2 * a) * NW + w]);
-				y = max(y, red[(2 * a + 1) * NW + w]);
-			}
+			int x, y, s;
+			bounds.get(a, x, y, s);
 			any = any && y >= x;
 			if (!any) break;
 			box[a] = x;
@@ -1684,35 +1666,24 @@ __global__ __launch_bounds__(kThreads) void k_deposit_cells(const double *__rest
 		}
 	}
 	const bool boxOk = t1 - t0 < 16;
-	int blo[3] = {0, 0, 0}, bn[3] = {1, 1, 1}, st[3] = {0, 0, 0};
-	int vol = 1;
+	int blo[3] = {0, 0, 0}, bn[3] = {1, 1, 1};
 #pragma unroll
 	for (int d = 0; d < ND; d++) {
 		int clo = tlo[d] * tg.tw, chi = min(thi[d] * tg.tw + tg.tw - 1, tg.cmax[d]);
 		blo[d] = clo - 1;
 		bn[d] = chi - clo + 4;  // nodes clo-1 .. chi+2
-		st[d] = vol;
-		vol *= bn[d];
 	}
-	if (!boxOk || vol > kDepCap) vol = 0;
-	for (int t = threadIdx.x; t < vol; t += kThreads) acc[t] = 0.0;
+	NodeBox<ND> nb(blo, bn);
+	if (!boxOk || nb.vol > kDepCap) nb.vol = 0;
+	nb.zero(acc, 1);
 	__syncthreads();
 
 	auto add8 = [&](const int *j, const double *w) {
-		bool inBox = vol > 0;
+		int l0;
+		const bool inBox = nb.index(j, l0);
+		if (nb.vol > 0 && inBox) {
 #pragma unroll
-		for (int d = 0; d < ND; d++) inBox = inBox && j[d] >= blo[d] && j[d] + 1 < blo[d] + bn[d];
-		if (inBox) {
-			int l0 = 0;
-#pragma unroll
-			for (int d = 0; d < ND; d++) l0 += (j[d] - blo[d]) * st[d];
-#pragma unroll
-			for (int c = 0; c < NC; c++) {
-				int off = l0;
-#pragma unroll
-				for (int d = 0; d < ND; d++) off += ((c >> d) & 1) ? st[d] : 0;
-				atomicAdd(&acc[off], w[c]);
-			}
+			for (int c = 0; c < NC; c++) atomicAdd(&acc[l0 + nb.corner(c)], w[c]);
 		} else {
 #pragma unroll
 			for (int c = 0; c < NC; c++) unsafeAtomicAdd(&rho[corner_off<ND>(G, j, c)], w[c]);
@@ -1730,17 +1701,11 @@ __global__ __launch_bounds__(kThreads) void k_deposit_cells(const double *__rest
 		for (int c = 0; c < NC; c++) sum[c] = 0.0;
 		bool any = false;
 		for (long i = a; i < b; i++) {
-			double dec[3], comp[3], w[NC];
+			double p[3], dec[3], comp[3], w[NC];
 			int j[3];
-			bool own = true;
 #pragma unroll
-			for (int d = 0; d < ND; d++) {
-				double p = xs[d][i];
-				j[d] = (int)p;
-				dec[d] = p - j[d];
-				comp[d] = 1 - dec[d];
-				own = own && j[d] == cell[d];
-			}
+			for (int d = 0; d < ND; d++) p[d] = xs[d][i];
+			const bool own = cell_split<ND, false>(p, G.T, cell, j, dec, comp);
 			cic_weights<ND, V3D>(dec, comp, w);
 			literal_ghost_weights<ND>(g, j, w);
 			if (own) {
@@ -1753,21 +1718,9 @@ __global__ __launch_bounds__(kThreads) void k_deposit_cells(const double *__rest
 		}
 		if (any) add8(cell, sum);
 	}
-	if (!vol) return;
+	if (!nb.vol) return;
 	__syncthreads();
-	for (int t = threadIdx.x; t < vol; t += kThreads) {
-		double v = acc[t];
-		if (v == 0.0) continue;
-		int r = t;
-		long off = 0;
-#pragma unroll
-		for (int d = 0; d < ND; d++) {
-			int c = r % bn[d];
-			r /= bn[d];
-			off += node_off(G, d, blo[d] + c);
-		}
-		unsafeAtomicAdd(&rho[off], v);
-	}
+	nb.flush(acc, 1, G, rho);
 }
 
 // ------------------------------------------------------- fused push -------
@@ -3272,7 +3225,7 @@ extern "C" int pinc_hip_deposit(pinc_pop_t pop, int s, pinc_geom_t g, double *rh
 	long n = pop.iStop[s] - pop.iStart[s];
 	if (n <= 0) return 0;
 	long b0 = pop.iStart[s];
-	long nb = ceil_div(n + (b0 & 1L), (long)kDepChunk);
+	long nb = chunk_blocks(b0, n, kDepChunk);
 	hipStream_t st = (hipStream_t)stream;
 	const double *x0 = pop.x[0];
 	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr;
@@ -3295,7 +3248,7 @@ extern "C" int pinc_hip_moments(pinc_pop_t pop, int s, pinc_geom_t g, const doub
 	long n = pop.iStop[s] - pop.iStart[s];
 	if (n <= 0) return 0;
 	long b0 = pop.iStart[s];
-	long nb = ceil_div(n + (b0 & 1L), (long)kMomChunk);
+	long nb = chunk_blocks(b0, n, kMomChunk);
 	hipStream_t st = (hipStream_t)stream;
 	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr, *x2 = g.nd > 2 ? pop.x[2] : nullptr;
 	const double *v1 = g.nd > 1 ? v[1] : nullptr, *v2 = g.nd > 2 ? v[2] : nullptr;
@@ -3329,7 +3282,7 @@ extern "C" int pinc_hip_phase_hist(pinc_pop_t pop, int s, const double *const v[
 		return set_error(hipErrorInvalidValue, "phase_hist: more than 2^24 bins");
 	const long b0 = pop.iStart[s], n = pop.iStop[s] - b0;
 	if (n <= 0) return 0;
-	const long nb = ceil_div(n + (b0 & 1L), (long)kPhChunk);
+	const long nb = chunk_blocks(b0, n, kPhChunk);
 	hipStream_t st = (hipStream_t)stream;
 	if (na == 1)
 		hipLaunchKernelGGL((k_phase_hist<1>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], b0, n, spec, hist, outside);

@@ -20,18 +20,16 @@ velocity arrays other than pop.v; two calls into one slab; M[0] against
 pinc_hip_deposit.
 """
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 import moments_ref as MR
 import push_ref as R
+from moments_cases import case
 from push_abi import SENTINEL, DevSpecies, Geom, Pop, geom_of
 
 pytestmark = pytest.mark.gpu
-
-TW = 4
 
 
 @pytest.fixture(scope="module")
@@ -45,55 +43,6 @@ def hip(built):
     h.pinc_hip_deposit.argtypes = [Pop, C.c_int, Geom, vp, vp]
     h.pinc_hip_fold_self_values.argtypes = [vp, Geom, C.c_int, vp]
     return h
-
-
-def extremes(geom, rng):
-    """particles in cell 0 and in cell T of each dimension (the others mid
-    domain), and in the lowest and the highest corner cell"""
-    nd = len(geom)
-    mid = np.array([t // 2 + 0.375 for t in geom])
-    rows = []
-    for d in range(nd):
-        for x in (0.25, geom[d] + 0.75):
-            p = mid.copy()
-            p[d] = x
-            rows.append(p)
-    rows.append(np.full(nd, 0.625))
-    rows.append(np.array([t + 0.125 for t in geom]))
-    pos = np.array(rows)
-    return pos, rng.uniform(-0.9, 0.9, size=pos.shape)
-
-
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """(geom, pos, vel, reference): made once, shared, never modified"""
-    rng = np.random.default_rng({"uniform3d": 11, "sorted3d": 12, "edge3d": 13, "2d": 14, "1d": 15}[name])
-    if name == "uniform3d":
-        geom = (8, 8, 8)
-        pos, vel = R.uniform_particles(geom, 5000, rng, R.V_MAX)
-    elif name in ("sorted3d", "edge3d"):
-        geom = (16, 8, 8)
-        pos, vel = R.uniform_particles(geom, 20000, rng, R.V_MAX)
-        pos, vel = R.cell_sorted(pos, vel, geom, TW)
-        if name == "edge3d":
-            pe, ve = R.edge_particles(geom)
-            px, vx = extremes(geom, rng)
-            pos, vel = np.concatenate([pos, pe, px]), np.concatenate([vel, ve, vx])
-    elif name == "2d":
-        geom = (16, 16)
-        pos, vel = R.uniform_particles(geom, 6000, rng, R.V_MAX)
-        pos, vel = R.cell_sorted(pos, vel, geom, 8)
-        pe, ve = R.edge_particles(geom)
-        px, vx = extremes(geom, rng)
-        pos, vel = np.concatenate([pos, pe, px]), np.concatenate([vel, ve, vx])
-    else:
-        geom = (64,)
-        pos, vel = R.uniform_particles(geom, 5000, rng, R.V_MAX)
-        px, vx = extremes(geom, rng)
-        pos, vel = np.concatenate([pos, px]), np.concatenate([vel, vx])
-    for a in (pos, vel):
-        a.setflags(write=False)
-    return geom, pos, vel, MR.moments_reference(pos, vel, geom)
 
 
 def slab_zeros(geom, nv):
