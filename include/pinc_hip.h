@@ -224,7 +224,7 @@ typedef struct {
 	int *holes;         /* >= nEmig+1 */
 	int *order;         /* >= nEmig   */
 	int *blockHist;     /* >= 28*ceil(nEmig/1024)+28 */
-	int *scratch;       /* >= 64 ints */
+	int *scratch;       /* >= 92 ints: [0] holes, [32, 60) base and [64, 92) count of each direction */
 	double *buf;        /* 6*cap doubles */
 	unsigned char *bufNe;
 	long cap;

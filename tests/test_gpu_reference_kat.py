@@ -32,6 +32,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from migrate_ref import ExtractWs
 from push_abi import Geom, Pop, PushArgs, device_pop as _device_pop
 
 pytestmark = pytest.mark.gpu
@@ -236,13 +237,6 @@ def test_pudistr3d1_known_answers_tiled_cells(hip):
     assert hip.pinc_hip_deposit_cells(out, 0, g, 4, ends, n, rho.data_ptr(), None) == 0
     torch.cuda.synchronize()
     _embedded_fractions(rho.cpu().numpy(), T, k)
-
-
-class ExtractWs(C.Structure):
-    """pinc_extract_ws_t (include/pinc_hip.h)."""
-    _fields_ = [("chunkOffset", C.c_void_p), ("scanWork", C.c_void_p), ("tail", C.c_void_p), ("holes", C.c_void_p),
-                ("order", C.c_void_p), ("blockHist", C.c_void_p), ("scratch", C.c_void_p), ("buf", C.c_void_p),
-                ("bufNe", C.c_void_p), ("cap", C.c_long)]
 
 
 @pytest.mark.parametrize("nd_method", ["puExtractEmigrants3D", "puExtractEmigrantsND"])
