@@ -227,6 +227,17 @@ funPtr puAccND0KE_set(dictionary *ini);
 funPtr puDistrND0_set(dictionary *ini);
 void puAccND0KE(Population *pop, Grid *E);
 void puDistrND0(const Population *pop, Grid *rho);
+/* order 2, quadratic B-spline over three nodes per dimension (an extension,
+ * not in the reference, whose puSanity anticipates it, pusher.c:1047-1087;
+ * the rule is at pinc_hip_deposit_tsc, include/pinc_hip.h).  With the one
+ * ghost layer the selectors accept only grid:thresholds = 0.5.  Not fused
+ * (population:fused is ignored); puAccND2_set returns puAccND2KE, as the
+ * order-0 pair does */
+funPtr puAccND2_set(dictionary *ini);
+funPtr puAccND2KE_set(dictionary *ini);
+funPtr puDistrND2_set(dictionary *ini);
+void puAccND2KE(Population *pop, Grid *E);
+void puDistrND2(const Population *pop, Grid *rho);
 funPtr puDistr3D1_set(dictionary *ini);
 funPtr puDistrND1_set(dictionary *ini);
 void puDistr3D1(const Population *pop, Grid *rho);

@@ -341,6 +341,37 @@ int pinc_hip_field_chain_all(const double *E, double *Es, long n, const double *
 int pinc_hip_deposit_ngp(pinc_pop_t pop, int s, pinc_geom_t g, double *rhoSlab, void *stream);
 int pinc_hip_accelerate_ngp(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es, double *kePartial,
                             int *nBlocks, void *stream);
+/* order 2 (quadratic B-spline, "TSC": three nodes per dimension), an
+ * extension: the reference's puSanity (pusher.c:1047-1087) anticipates the
+ * order without shipping its operators.  The weighting rule is fixed, so that
+ * it can be restated exactly (no fused multiply-add in this library).  Per
+ * dimension d, with T_d the true nodes (nloc in the slab dimension) and x_d
+ * the position in the local frame, in fp64 and this order:
+ *     j    = min(max((int)(x_d + 0.5), 1), T_d)      nearest true node, clamped
+ *     dl   = x_d - j
+ *     w[0] = 0.5 * ((0.5 - dl) * (0.5 - dl))         node j - 1
+ *     w[1] = 0.75 - dl * dl                          node j
+ *     w[2] = 0.5 * ((0.5 + dl) * (0.5 + dl))         node j + 1
+ * A node's weight is the product of its per-dimension weights taken in the
+ * order d = nd-1 .. 0: w_0 * (w_1 * w_2) in 3-D, w_0 * w_1 in 2-D.  That gives
+ * 3^nd nodes in padded coordinates 0 .. T_d + 1, for positions in
+ * [0.5, T_d + 0.5) (grid:thresholds = 0.5 with the one ghost layer).  The
+ * clamp is part of the rule: at dl = +-0.5 the weights relative to j equal
+ * those relative to j +- 1, so the rule is continuous at the clamp, and a
+ * position that rounding has put on T_d + 0.5 still lands on nodes <= T_d + 1.
+ *   deposit_tsc     adds the raw weights of species s to rhoSlab (accumulated,
+ *                   never cleared; the caller applies the 1/q, q chain);
+ *                   g.literal multiplies each node's weight as
+ *                   pinc_hip_deposit_ngp does
+ *   accelerate_tsc  dv_d = sum over the nodes of w Es[node nd + d], the nodes
+ *                   in the order i_0 + 3 i_1 + 9 i_2 ascending; v += dv, KE
+ *                   partials of v.(v + dv) as pinc_hip_accelerate_ngp (at most
+ *                   ceil(n / 2048) blocks)
+ * Errors (nothing is launched): nd outside 1..3, s outside the population's
+ * species, a null array. */
+int pinc_hip_deposit_tsc(pinc_pop_t pop, int s, pinc_geom_t g, double *rhoSlab, void *stream);
+int pinc_hip_accelerate_tsc(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es, double *kePartial,
+                            int *nBlocks, void *stream);
 /* pVelAssertMax (population.c:342-365) over species s: a velocity component
  * above maxVel sets bit 0 of *errFlag */
 int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *errFlag, void *stream);

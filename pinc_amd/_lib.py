@@ -202,6 +202,25 @@ HIP.pinc_hip_error_string.restype = C.c_char_p
 HIP.pinc_hip_device_count.argtypes = [C.POINTER(C.c_int)]
 
 
+class HipGeom(C.Structure):
+    """pinc_geom_t (include/pinc_hip.h)"""
+    _fields_ = [("nd", C.c_int), ("T", C.c_int * 3), ("nloc", C.c_int), ("off", C.c_int), ("nranks", C.c_int),
+                ("literal", C.c_int)]
+
+
+class HipPop(C.Structure):
+    """pinc_pop_t (include/pinc_hip.h)"""
+    _fields_ = [("x", C.c_void_p * 3), ("v", C.c_void_p * 3), ("nSpecies", C.c_int), ("nd", C.c_int),
+                ("iStart", C.c_long * 9), ("iStop", C.c_long * 8)]
+
+
+# order 2 (quadratic spline): pop, s, geom, rhoSlab, stream / pop, s, geom, Es, kePartial, nBlocks, stream
+HIP.pinc_hip_deposit_tsc.restype = C.c_int
+HIP.pinc_hip_deposit_tsc.argtypes = [HipPop, C.c_int, HipGeom, C.c_void_p, C.c_void_p]
+HIP.pinc_hip_accelerate_tsc.restype = C.c_int
+HIP.pinc_hip_accelerate_tsc.argtypes = [HipPop, C.c_int, HipGeom, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+
+
 def comm_unique_id() -> bytes:
     buf = (C.c_ubyte * PINC_COMM_ID_BYTES)()
     rc = HIP.pinc_hip_comm_unique_id(buf)

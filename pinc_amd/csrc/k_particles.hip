@@ -372,8 +372,8 @@ __device__ __forceinline__ long node_off(const Geo &G, int d, int p) {
 
 // --------------------------------------------- LDS-privatised deposit -----
 // The frame shared by the kernels that scatter a species through an LDS box
-// owned by the workgroup (k_deposit_tiled, k_moments, k_phase_hist; the box
-// also k_deposit_cells), each piece written once below:
+// owned by the workgroup (k_deposit_tiled, k_moments, k_phase_hist,
+// k_deposit_tsc; the box also k_deposit_cells), each piece written once below:
 //  * ChunkItems: a workgroup owns a chunk of kThreads * ITEMS consecutive
 //    particles, a thread ITEMS consecutive ones, loaded 16 B at a time from
 //    the 16-byte aligned slot at or below iStart; the guards of an odd iStart
@@ -382,7 +382,8 @@ __device__ __forceinline__ long node_off(const Geo &G, int d, int p) {
 //    bounds, and one more count, through DPP wave reductions and LDS.  Which
 //    box follows from them is each kernel's policy;
 //  * NodeBox: a box of grid nodes in LDS: zero(), the index of a cell whose
-//    upper neighbours are inside too, the corners' offsets, and the flush with
+//    upper neighbours are inside too (of a node whose lower and upper
+//    neighbours are: the order-2 stencil), the corners' offsets, and the flush with
 //    one global atomic per value that is not zero;
 //  * cell_split: a particle's cell, the fractions of its CIC weights, and
 //    whether it continues the thread's run of particles in one cell.
@@ -671,6 +672,19 @@ struct NodeBox {
 			const int r = cell[d] - lo[d];
 			in = in && r >= 0 && r + 1 < n[d];
 			l0 += r * st[d];
+		}
+		return in;
+	}
+	// l: the linear index of `node`; true if its lower and upper neighbours
+	// are inside the box too (a three-node stencil per dimension)
+	__device__ __forceinline__ bool index_centre(const int *node, int &l) const {
+		bool in = true;
+		l = 0;
+#pragma unroll
+		for (int d = 0; d < ND; d++) {
+			const int r = node[d] - lo[d];
+			in = in && r >= 1 && r + 1 < n[d];
+			l += r * st[d];
 		}
 		return in;
 	}
@@ -3031,6 +3045,251 @@ __global__ __launch_bounds__(kThreads) void k_accel_ngp(const double *__restrict
 	if (threadIdx.x == 0) kePartial[blockIdx.x] = t;
 }
 
+// ------------------------------------- order 2 (quadratic spline) ---------
+// puDistrND2 / puAccND2KE (an extension; the reference's puSanity anticipates
+// order 2, pusher.c:1047-1087): the quadratic B-spline over the nearest true
+// node j and its two neighbours per dimension, the rule of include/pinc_hip.h.
+// j is clamped to 1..T, so the stencil stays on the padded nodes 0..T+1
+// whatever the position holds.
+
+// nearest true node j[d] and the three one-dimensional weights w1[d][0..2] of
+// nodes j-1, j, j+1; true if j is the node cj of the thread's current run
+template <int ND>
+__device__ __forceinline__ bool tsc_split(const double *x, const int *T, const int *cj, int *j, double (*w1)[3]) {
+	bool same = true;
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+		j[d] = min(max((int)(x[d] + 0.5), 1), T[d]);
+		const double dl = x[d] - j[d];
+		const double a = 0.5 - dl, b = 0.5 + dl;
+		w1[d][0] = 0.5 * (a * a);
+		w1[d][1] = 0.75 - dl * dl;
+		w1[d][2] = 0.5 * (b * b);
+		same = same && (j[d] == cj[d]);
+	}
+	return same;
+}
+
+// stencil index of node c = i0 + 3 i1 + 9 i2 along dimension d (0..2: j-1..j+1)
+__device__ __forceinline__ constexpr int tsc_digit(int c, int d) { return d == 0 ? c % 3 : d == 1 ? (c / 3) % 3 : c / 9; }
+
+// the 3^ND node weights, the product taken in the order d = ND-1 .. 0 as
+// cic_weights' general form
+template <int ND>
+__device__ __forceinline__ void tsc_weights(const double (*w1)[3], double *w) {
+	constexpr int NN = ND == 3 ? 27 : ND == 2 ? 9 : 3;
+#pragma unroll
+	for (int c = 0; c < NN; c++) {
+		double f = 1.0;
+#pragma unroll
+		for (int d = ND - 1; d >= 1; d--) f = w1[d][tsc_digit(c, d)] * f;
+		w[c] = w1[0][tsc_digit(c, 0)] * f;
+	}
+}
+
+// the same for the nodes of one layer: index c = i0 + 3 i1 within the layer lz
+// of the last dimension in 3-D (c alone below that)
+__device__ __forceinline__ int tsc_layer_digit(int c, int lz, int d) { return d == 2 ? lz : tsc_digit(c, d); }
+template <int ND>
+__device__ __forceinline__ void tsc_layer_weights(const double (*w1)[3], int lz, double *w) {
+	if constexpr (ND < 3) {
+		tsc_weights<ND>(w1, w);
+	} else {
+		const double wz = lz == 0 ? w1[2][0] : lz == 1 ? w1[2][1] : w1[2][2];
+#pragma unroll
+		for (int c = 0; c < 9; c++) w[c] = w1[0][c % 3] * (w1[1][c / 3] * wz);
+	}
+}
+
+// global offset of stencil node c of the stencil centred on padded node j
+template <int ND>
+__device__ __forceinline__ long tsc_node_off(const Geo &G, const int *j, int c) {
+	long off = 0;
+#pragma unroll
+	for (int d = 0; d < ND; d++) off += node_off(G, d, j[d] - 1 + tsc_digit(c, d));
+	return off;
+}
+
+// k_deposit_tiled's frame with the three-node stencil: the chunk's box spans
+// [min j - 1, max j + 1] per dimension; a run of consecutive particles with one
+// nearest node is summed in 3^ND registers and added once.
+template <int ND>
+__global__ __launch_bounds__(kThreads) void k_deposit_tsc(const double *__restrict__ x0,
+                                                          const double *__restrict__ x1,
+                                                          const double *__restrict__ x2, long b0, long n,
+                                                          pinc_geom_t g, double *__restrict__ rho) {
+	constexpr int NN = ND == 3 ? 27 : ND == 2 ? 9 : 3;
+	g.nd = ND;  // (the launcher's choice of instance, here a constant: the slab dimension folds)
+	__shared__ double acc[kDepCap];
+	__shared__ BlockBounds<3, false, false> bounds;
+	__shared__ int box[7];
+	Geo G = make_geo(g);
+	const double *xs[3] = {x0, x1, x2};
+	const ChunkItems<kDepItems> ch(b0, n);
+
+	// pass 1: bounds of the chunk's nearest nodes
+	int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+#pragma unroll
+		for (int k = 0; k < kDepItems; k += 2) {
+			double x[2];
+			ch.load2(xs[d], k, x[0], x[1]);
+#pragma unroll
+			for (int h = 0; h < 2; h++)
+				if (ch.live(k + h)) {
+					const int c = min(max((int)(x[h] + 0.5), 1), G.T[d]);
+					lo[d] = min(lo[d], c);
+					hi[d] = max(hi[d], c);
+				}
+		}
+	}
+	bounds.reduce(ND, lo, hi, nullptr, 0);
+	if (threadIdx.x == 0) {
+		long vol = 1;
+		for (int d = 0; d < ND; d++) {
+			int a, b, s;
+			bounds.get(d, a, b, s);
+			box[d] = a - 1;
+			box[3 + d] = b - a + 3;
+			vol *= (long)(b - a + 3);
+		}
+		box[6] = (vol <= kDepCap && vol > 0) ? (int)vol : 0;
+	}
+	__syncthreads();
+
+	NodeBox<ND> nb;
+	if (box[6]) {
+		nb = NodeBox<ND>(box, box + 3);
+		nb.zero(acc, 1);
+		__syncthreads();
+	}
+
+	// pass 2: runs of equal nearest nodes summed in registers, NA nodes at a
+	// time: all 3^ND in 1-D and 2-D, one z-layer of nine per pass over the
+	// thread's particles in 3-D (27 accumulators next to 27 weights and the
+	// adds' addresses took 248 VGPRs and spilled scalar registers; the
+	// particles of the later passes come from cache).  One particle per turn
+	// and one more turn for the last run, so that a run's adds are in the
+	// code once; pairs are still loaded 16 B wide.
+	constexpr int NL = ND == 3 ? 3 : 1, NA = NN / NL;
+#pragma unroll 1
+	for (int lz = 0; lz < NL; lz++) {
+		int cj[3] = {INT32_MIN, 0, 0};
+		double a[NA];
+#pragma unroll
+		for (int c = 0; c < NA; c++) a[c] = 0.0;
+		double pp[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll 1
+		for (int k = 0; k <= kDepItems; k++) {
+			const bool last = k == kDepItems;
+			if (!last && !(k & 1)) {
+#pragma unroll
+				for (int d = 0; d < ND; d++) ch.load2(xs[d], k, pp[0][d], pp[1][d]);
+			}
+			const bool lv = !last && ch.live(k);
+			if (!last && !lv) continue;
+			// (On the extra turn x is the last pair again and lv is false: j is
+			// clamped, so nothing is out of range, `same` is false and the weights
+			// are dropped.  Skipping their computation under `if (lv)` costs the
+			// 3-D instance 49 VGPRs and a wave of occupancy, so it stays.)
+			double x[3], w1[3][3], w[NA];
+			int j[3];
+#pragma unroll
+			for (int d = 0; d < ND; d++) x[d] = (k & 1) ? pp[1][d] : pp[0][d];
+			const bool same = tsc_split<ND>(x, G.T, cj, j, w1) && lv;
+			tsc_layer_weights<ND>(w1, lz, w);
+			if (g.literal) {
+#pragma unroll
+				for (int c = 0; c < NA; c++) {
+					int p[3];
+#pragma unroll
+					for (int d = 0; d < ND; d++) p[d] = j[d] - 1 + tsc_layer_digit(c, lz, d);
+					w[c] *= literal_node_factor<ND>(g, p);
+				}
+			}
+			if (same) {
+#pragma unroll
+				for (int c = 0; c < NA; c++) a[c] += w[c];
+				continue;
+			}
+			// the run ends: add it (the bounding box holds every run's stencil)
+			if (cj[0] != INT32_MIN) {
+				if (nb.vol) {
+					int l;
+					nb.index_centre(cj, l);
+#pragma unroll
+					for (int c = 0; c < NA; c++) {
+						int off = l;
+#pragma unroll
+						for (int d = 0; d < ND; d++) off += (tsc_layer_digit(c, lz, d) - 1) * nb.st[d];
+						atomicAdd(&acc[off], a[c]);
+					}
+				} else {
+#pragma unroll
+					for (int c = 0; c < NA; c++) {
+						long off = 0;
+#pragma unroll
+						for (int d = 0; d < ND; d++) off += node_off(G, d, cj[d] - 1 + tsc_layer_digit(c, lz, d));
+						unsafeAtomicAdd(&rho[off], a[c]);
+					}
+				}
+			}
+#pragma unroll
+			for (int c = 0; c < NA; c++) a[c] = w[c];
+#pragma unroll
+			for (int d = 0; d < ND; d++) cj[d] = j[d];
+		}
+	}
+	if (!nb.vol) return;
+	__syncthreads();
+	nb.flush(acc, 1, G, rho);
+}
+
+// k_accel_ngp's chunking and KE partials; dv_d = sum over the 3^ND nodes of
+// w Es[node ND + d], nodes in the order c = 0 .. 3^ND - 1, gathered through L2
+template <int ND>
+__global__ __launch_bounds__(kThreads) void k_accel_tsc(const double *__restrict__ x0, const double *__restrict__ x1,
+                                                        const double *__restrict__ x2, double *__restrict__ v0,
+                                                        double *__restrict__ v1, double *__restrict__ v2, long b0,
+                                                        long n, pinc_geom_t g, const double *__restrict__ E,
+                                                        double *__restrict__ kePartial) {
+	constexpr int NN = ND == 3 ? 27 : ND == 2 ? 9 : 3;
+	__shared__ double red[kThreads / 64];
+	g.nd = ND;
+	Geo G = make_geo(g);
+	const double *xs[3] = {x0, x1, x2};
+	double *vs[3] = {v0, v1, v2};
+	const int none[3] = {0, 0, 0};
+	double ke = 0.0;
+	for (int k = 0; k < kAccItems; k++) {
+		const long i = (long)blockIdx.x * kAccChunk + (long)k * kThreads + threadIdx.x;
+		if (i >= n) break;
+		double x[3], w1[3][3], w[NN], dv[3] = {0.0, 0.0, 0.0};
+		int j[3];
+#pragma unroll
+		for (int d = 0; d < ND; d++) x[d] = xs[d][b0 + i];
+		tsc_split<ND>(x, G.T, none, j, w1);
+		tsc_weights<ND>(w1, w);
+#pragma unroll
+		for (int c = 0; c < NN; c++) {
+			const long off = tsc_node_off<ND>(G, j, c) * ND;
+#pragma unroll
+			for (int d = 0; d < ND; d++) dv[d] += w[c] * E[off + d];
+		}
+		double vsq = 0.0;
+#pragma unroll
+		for (int d = 0; d < ND; d++) {
+			const double vv = vs[d][b0 + i];
+			vsq += vv * (vv + dv[d]);
+			vs[d][b0 + i] = vv + dv[d];
+		}
+		ke += vsq;
+	}
+	const double t = block_sum(ke, red);
+	if (threadIdx.x == 0) kePartial[blockIdx.x] = t;
+}
+
 // pVelAssertMax (population.c:342-365): a component above maxVel (signed, as
 // the reference) sets bit 0 of the assert word
 __global__ __launch_bounds__(kThreads) void k_vel_assert(const double *__restrict__ v0, const double *__restrict__ v1,
@@ -3089,6 +3348,57 @@ extern "C" int pinc_hip_accelerate_ngp(pinc_pop_t pop, int s, pinc_geom_t g, con
 		hipLaunchKernelGGL(k_accel_ngp<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], nullptr, nullptr, pop.v[0],
 		                   nullptr, nullptr, b0, n, g, Es, kePartial);
 	return check_launch("accelerate (NGP)");
+}
+
+// a species index and dimensions the order-2 entry points accept
+static int tsc_args_ok(const pinc_pop_t &pop, int s, const pinc_geom_t &g) {
+	if (g.nd < 1 || g.nd > 3 || s < 0 || s >= PINC_MAX_SPECIES || s >= pop.nSpecies) return 0;
+	for (int d = 0; d < g.nd; d++)
+		if (!pop.x[d] || g.T[d] < 1) return 0;
+	return g.nloc >= 1;
+}
+
+extern "C" int pinc_hip_deposit_tsc(pinc_pop_t pop, int s, pinc_geom_t g, double *rho, void *stream) {
+	if (!tsc_args_ok(pop, s, g) || !rho)
+		return set_error(hipErrorInvalidValue, "deposit (order 2): bad species, dimensions or null array");
+	long n = pop.iStop[s] - pop.iStart[s];
+	if (n <= 0) return 0;
+	long b0 = pop.iStart[s];
+	long nb = chunk_blocks(b0, n, kDepChunk);
+	hipStream_t st = (hipStream_t)stream;
+	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr, *x2 = g.nd > 2 ? pop.x[2] : nullptr;
+	if (g.nd == 3)
+		hipLaunchKernelGGL(k_deposit_tsc<3>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
+	else if (g.nd == 2)
+		hipLaunchKernelGGL(k_deposit_tsc<2>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
+	else
+		hipLaunchKernelGGL(k_deposit_tsc<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
+	return check_launch("deposit (order 2)");
+}
+
+extern "C" int pinc_hip_accelerate_tsc(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es, double *kePartial,
+                                       int *nBlocks, void *stream) {
+	if (nBlocks) *nBlocks = 0;
+	if (!tsc_args_ok(pop, s, g) || !Es || !kePartial || !nBlocks)
+		return set_error(hipErrorInvalidValue, "accelerate (order 2): bad species, dimensions or null array");
+	for (int d = 0; d < g.nd; d++)
+		if (!pop.v[d]) return set_error(hipErrorInvalidValue, "accelerate (order 2): null velocity array");
+	long n = pop.iStop[s] - pop.iStart[s];
+	if (n <= 0) return 0;
+	long b0 = pop.iStart[s];
+	long nb = ceil_div(n, (long)kAccChunk);
+	*nBlocks = (int)nb;
+	hipStream_t st = (hipStream_t)stream;
+	if (g.nd == 3)
+		hipLaunchKernelGGL(k_accel_tsc<3>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], pop.x[2], pop.v[0],
+		                   pop.v[1], pop.v[2], b0, n, g, Es, kePartial);
+	else if (g.nd == 2)
+		hipLaunchKernelGGL(k_accel_tsc<2>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], nullptr, pop.v[0],
+		                   pop.v[1], nullptr, b0, n, g, Es, kePartial);
+	else
+		hipLaunchKernelGGL(k_accel_tsc<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], nullptr, nullptr, pop.v[0],
+		                   nullptr, nullptr, b0, n, g, Es, kePartial);
+	return check_launch("accelerate (order 2)");
 }
 
 extern "C" int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *errFlag, void *stream) {

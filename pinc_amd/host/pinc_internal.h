@@ -202,7 +202,7 @@ struct PincDevGrid {
 	int extStale;       /* owned planes written (gSyncToDevice), halo not yet refreshed */
 	/* main.c's second gHaloOp(addSlice, rho, FROMHALO) of a step
 	 * (main.c:226,232): the population of the last deposit, its order (0 NGP,
-	 * 1 CIC) and the folds since; lit is the scratch of the missing weight */
+	 * 1 CIC, 2 quadratic spline) and the folds since; lit is the scratch of the missing weight */
 	const Population *depPop;
 	int depOrder, folds;
 	double *lit;

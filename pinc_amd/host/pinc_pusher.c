@@ -120,6 +120,12 @@ funPtr puBoris3D1KE_set(dictionary *ini) {
 funPtr puAccND0_set(dictionary *ini) { puSanity(ini, "puAccND0", 0, 0); return (funPtr)puAccND0KE; }
 funPtr puAccND0KE_set(dictionary *ini) { puSanity(ini, "puAccND0KE", 0, 0); return (funPtr)puAccND0KE; }
 funPtr puDistrND0_set(dictionary *ini) { puSanity(ini, "puDistrND0", 0, 0); return (funPtr)puDistrND0; }
+/* order 2 (quadratic spline, an extension): with one ghost layer puSanity
+ * leaves grid:thresholds = 0.5 only; puAccND2_set returns the KE variant, as
+ * the order-0 pair */
+funPtr puAccND2_set(dictionary *ini) { puSanity(ini, "puAccND2", 0, 2); return (funPtr)puAccND2KE; }
+funPtr puAccND2KE_set(dictionary *ini) { puSanity(ini, "puAccND2KE", 0, 2); return (funPtr)puAccND2KE; }
+funPtr puDistrND2_set(dictionary *ini) { puSanity(ini, "puDistrND2", 0, 2); return (funPtr)puDistrND2; }
 funPtr puDistr3D1_set(dictionary *ini) { puSanity(ini, "puDistr3D1", 3, 1); return (funPtr)puDistr3D1; }
 funPtr puDistrND1_set(dictionary *ini) { puSanity(ini, "puDistrND1", 0, 1); return (funPtr)puDistrND1; }
 funPtr puExtractEmigrants3D_set(dictionary *ini) {
@@ -1077,6 +1083,30 @@ void puDistrND0(const Population *pop, Grid *rho) {
 	pinc_phase_end(3);
 }
 
+/* gZero; per species gMul(1/q), the quadratic-spline weights of every
+ * particle on the 3^nd nodes around its nearest one, gMul(q): puDistrND0's
+ * chain with pinc_hip_deposit_tsc.  A fused push's CIC deposit is not used. */
+void puDistrND2(const Population *pop, Grid *rho) {
+	pinc_pop_flush_host(pop);
+	pinc_phase_begin(3);
+	PincDevGrid *g = rho->dev;
+	g->depPop = pop;
+	g->depOrder = 2;
+	g->folds = 0;
+	pop->dev->depValid = pop->dev->depExtracted = 0;
+	pinc_check(pinc_hip_zero(g->d, g->n, g_pinc.stream), "distr zero");
+	pinc_pop_t p = pinc_devpop(pop);
+	for (int s = 0; s < pop->nSpecies; s++) {
+		if (s > 0)
+			pinc_check(pinc_hip_scale2(g->d, g->n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream),
+			           "distr scale");
+		pinc_check(pinc_hip_deposit_tsc(p, s, g->geom, g->d, g_pinc.stream), "deposit (order 2)");
+	}
+	pinc_check(pinc_hip_scale(g->d, g->n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "distr scale");
+	g->ghostsValid = 0;
+	pinc_phase_end(3);
+}
+
 /* main.c:226 and :232 both call gHaloOp(addSlice, rho, FROMHALO) on one
  * deposit; ghost values are not cleared in between, so a
  * weight on a node with g ghost coordinates counts 2^g times.  Slab ghost
@@ -1097,6 +1127,7 @@ void pinc_literal_second_fold(const Population *pop, Grid *rho, int order) {
 			pinc_check(pinc_hip_scale2(g->lit, g->n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream),
 			           "second fold scale");
 		if (order == 0) pinc_check(pinc_hip_deposit_ngp(p, s, geo, g->lit, g_pinc.stream), "second fold (NGP)");
+		else if (order == 2) pinc_check(pinc_hip_deposit_tsc(p, s, geo, g->lit, g_pinc.stream), "second fold (order 2)");
 		else pinc_check(pinc_hip_deposit(p, s, geo, g->lit, g_pinc.stream), "second fold");
 	}
 	pinc_check(pinc_hip_scale(g->lit, g->n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "second fold scale");
@@ -1352,6 +1383,31 @@ void puAccND0KE(Population *pop, Grid *E) {
 		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream), "E chain");
 		pinc_check(pinc_hip_accelerate_ngp(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
 		           "accelerate (NGP)");
+		if (nb > 0) pinc_check(pinc_hip_sum(dv->kePartial, nb, g_pinc.dScratch, PINC_SLOT(16 + s), g_pinc.stream), "ke");
+		else pinc_check(pinc_hip_memset(PINC_SLOT(16 + s), 0, sizeof(double), g_pinc.stream), "ke");
+	}
+	double sums[PINC_MAX_SPECIES];
+	pinc_check(pinc_hip_d2h(sums, PINC_SLOT(16), ns * sizeof(double), g_pinc.stream), "ke readback");
+	for (int s = 0; s < ns; s++) pop->kinEnergy[s] = sums[s] * (0.5 * pop->mass[s]);
+	pinc_phase_end(6);
+}
+
+/* puAccND2KE: puAccND0KE's sequence with the quadratic-spline gather
+ * (pinc_hip_accelerate_tsc).  Not fused: the next puMove moves on its own. */
+void puAccND2KE(Population *pop, Grid *E) {
+	pinc_pop_flush_host(pop);
+	pinc_phase_begin(6);
+	PincDevPop *dv = pop->dev;
+	if (dv->pending) msg(ERROR, "puAccND2KE after a fused puAcc without its puMove");
+	pinc_pop_t p = pinc_devpop(pop);
+	int ns = pop->nSpecies;
+	PincDevGrid *eg = E->dev;
+	if (!eg->scaled) pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
+	for (int s = 0; s < ns; s++) {
+		int nb = 0;
+		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream), "E chain");
+		pinc_check(pinc_hip_accelerate_tsc(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
+		           "accelerate (order 2)");
 		if (nb > 0) pinc_check(pinc_hip_sum(dv->kePartial, nb, g_pinc.dScratch, PINC_SLOT(16 + s), g_pinc.stream), "ke");
 		else pinc_check(pinc_hip_memset(PINC_SLOT(16 + s), 0, sizeof(double), g_pinc.stream), "ke");
 	}

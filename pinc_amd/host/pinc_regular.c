@@ -222,8 +222,10 @@ static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
 	}
 	/* method selection (main.c:55-79) */
 	S->acc = (void (*)(Population *, Grid *))select(ini, "methods:acc", puAcc3D1_set, puAcc3D1KE_set, puAccND1_set,
-	                                                 puAccND1KE_set, puBoris3D1_set, puBoris3D1KE_set);
-	S->distr = (void (*)(const Population *, Grid *))select(ini, "methods:distr", puDistr3D1_set, puDistrND1_set);
+	                                                 puAccND1KE_set, puBoris3D1_set, puBoris3D1KE_set, puAccND2_set,
+	                                                 puAccND2KE_set);
+	S->distr = (void (*)(const Population *, Grid *))select(ini, "methods:distr", puDistr3D1_set, puDistrND1_set,
+	                                                        puDistrND2_set);
 	S->extractEmigrants = (void (*)(Population *, MpiInfo *))select(ini, "methods:migrate", puExtractEmigrants3D_set,
 	                                                                puExtractEmigrantsND_set);
 	void (*solverInterface)() = select(ini, "methods:poisson", mgSolver_set, sSolver_set);
