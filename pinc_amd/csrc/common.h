@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "pinc_hip.h"
 
 #define PINC_WAVE 64
@@ -11,6 +12,33 @@ namespace pinc {
 // error bookkeeping shared by all translation units (runtime.hip)
 int set_error(hipError_t e, const char *where);
 int check_launch(const char *where);
+
+// ---- host-side launch helpers of the C ABI ----
+// f(std::integral_constant<int, ND>) for the kernel instance of nd
+// dimensions: 3, 2, and the 1-D instance for anything else
+template <class F>
+inline void with_nd(int nd, F &&f) {
+	if (nd == 3) f(std::integral_constant<int, 3>{});
+	else if (nd == 2) f(std::integral_constant<int, 2>{});
+	else f(std::integral_constant<int, 1>{});
+}
+
+// live particles of species s: indices b0 .. b0 + n - 1
+struct Span {
+	long b0, n;
+};
+inline Span species_span(const pinc_pop_t &pop, int s) { return {pop.iStart[s], pop.iStop[s] - pop.iStart[s]}; }
+
+// the per-dimension pointers p[0..2] as kernel arguments: null above nd,
+// the others advanced by b0
+template <class T>
+struct Ptr3 {
+	T *a, *b, *c;
+};
+template <class T>
+inline Ptr3<T> upto_nd(T *const *p, int nd, long b0 = 0) {
+	return {p[0] + b0, nd > 1 ? p[1] + b0 : nullptr, nd > 2 ? p[2] + b0 : nullptr};
+}
 
 // storage index of a padded coordinate p (0..T+1) in a periodic dimension
 // stored without ghosts (grid.c halo semantics: ghost 0 == T, T+1 == 1)

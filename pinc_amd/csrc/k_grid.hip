@@ -262,9 +262,9 @@ extern "C" int pinc_hip_slab_from_global(double *slab, const double *global, pin
                                          void *stream) {
 	long n = plane_size(g) * (g.nloc + 2);
 	hipStream_t st = (hipStream_t)stream;
-	if (g.nd == 3) hipLaunchKernelGGL(k_slab_from_global<3>, dim3(grid_for(n)), dim3(kThreads), 0, st, slab, global, g, nValues);
-	else if (g.nd == 2) hipLaunchKernelGGL(k_slab_from_global<2>, dim3(grid_for(n)), dim3(kThreads), 0, st, slab, global, g, nValues);
-	else hipLaunchKernelGGL(k_slab_from_global<1>, dim3(grid_for(n)), dim3(kThreads), 0, st, slab, global, g, nValues);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_slab_from_global<ND>, dim3(grid_for(n)), dim3(kThreads), 0, st, slab, global, g, nValues);
+	});
 	return check_launch("slab_from_global");
 }
 
@@ -292,14 +292,12 @@ extern "C" int pinc_hip_efield_scaled(const double *phi, pinc_geom_t g, double *
 	hipStream_t st = (hipStream_t)stream;
 	if (plane_size(g) < (1L << 31) && g.nloc + 2 <= 65535) {
 		const dim3 grid((unsigned)ceil_div(plane_size(g), kThreads), (unsigned)(g.nloc + 2));
-		if (g.nd == 3) hipLaunchKernelGGL(k_efield_planes<3>, grid, dim3(kThreads), 0, st, phi, g, E, h);
-		else if (g.nd == 2) hipLaunchKernelGGL(k_efield_planes<2>, grid, dim3(kThreads), 0, st, phi, g, E, h);
-		else hipLaunchKernelGGL(k_efield_planes<1>, grid, dim3(kThreads), 0, st, phi, g, E, h);
+		with_nd(g.nd, [&](auto ND) { hipLaunchKernelGGL(k_efield_planes<ND>, grid, dim3(kThreads), 0, st, phi, g, E, h); });
 		return check_launch("efield");
 	}
-	if (g.nd == 3) hipLaunchKernelGGL(k_efield<3>, dim3(grid_for(n)), dim3(kThreads), 0, st, phi, g, E, h);
-	else if (g.nd == 2) hipLaunchKernelGGL(k_efield<2>, dim3(grid_for(n)), dim3(kThreads), 0, st, phi, g, E, h);
-	else hipLaunchKernelGGL(k_efield<1>, dim3(grid_for(n)), dim3(kThreads), 0, st, phi, g, E, h);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_efield<ND>, dim3(grid_for(n)), dim3(kThreads), 0, st, phi, g, E, h);
+	});
 	return check_launch("efield");
 }
 

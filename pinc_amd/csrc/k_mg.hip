@@ -1721,9 +1721,7 @@ extern "C" int pinc_hip_residual(double *res, const double *phi, const double *r
 	if (npts(L) >= (1L << 31)) return set_error(hipErrorInvalidValue, "residual: level too large for 32-bit indexing");
 	hipStream_t st = (hipStream_t)stream;
 	unsigned nb = blocks_for(npts(L));
-	if (L.nd == 3) hipLaunchKernelGGL(k_residual<3>, dim3(nb), dim3(kThreads), 0, st, res, phi, rho, L);
-	else if (L.nd == 2) hipLaunchKernelGGL(k_residual<2>, dim3(nb), dim3(kThreads), 0, st, res, phi, rho, L);
-	else hipLaunchKernelGGL(k_residual<1>, dim3(nb), dim3(kThreads), 0, st, res, phi, rho, L);
+	with_nd(L.nd, [&](auto ND) { hipLaunchKernelGGL(k_residual<ND>, dim3(nb), dim3(kThreads), 0, st, res, phi, rho, L); });
 	return check_launch("residual");
 }
 
@@ -1738,9 +1736,11 @@ extern "C" int pinc_hip_residual_sumsq(const double *phi, const double *rho, pin
 		nb = blocks_for(npts(L) / 2);
 		*nBlocks = (int)nb;
 		hipLaunchKernelGGL(k_residual_sumsq3p, dim3(nb), dim3(kThreads), 0, st, phi, rho, L, partial);
-	} else if (L.nd == 3) hipLaunchKernelGGL(k_residual_sumsq<3>, dim3(nb), dim3(kThreads), 0, st, phi, rho, L, partial);
-	else if (L.nd == 2) hipLaunchKernelGGL(k_residual_sumsq<2>, dim3(nb), dim3(kThreads), 0, st, phi, rho, L, partial);
-	else hipLaunchKernelGGL(k_residual_sumsq<1>, dim3(nb), dim3(kThreads), 0, st, phi, rho, L, partial);
+	} else {
+		with_nd(L.nd, [&](auto ND) {
+			hipLaunchKernelGGL(k_residual_sumsq<ND>, dim3(nb), dim3(kThreads), 0, st, phi, rho, L, partial);
+		});
+	}
 	return check_launch("residual_sumsq");
 }
 
@@ -1759,9 +1759,7 @@ extern "C" int pinc_hip_prolong_add(double *phiF, const double *phiC, pinc_lvl_t
 	if (npts(Lf) >= (1L << 31)) return set_error(hipErrorInvalidValue, "prolong_add: level too large for 32-bit indexing");
 	hipStream_t st = (hipStream_t)stream;
 	unsigned nb = blocks_for(npts(Lf));
-	if (Lf.nd == 3) hipLaunchKernelGGL(k_prolong_add<3>, dim3(nb), dim3(kThreads), 0, st, phiF, phiC, Lf);
-	else if (Lf.nd == 2) hipLaunchKernelGGL(k_prolong_add<2>, dim3(nb), dim3(kThreads), 0, st, phiF, phiC, Lf);
-	else hipLaunchKernelGGL(k_prolong_add<1>, dim3(nb), dim3(kThreads), 0, st, phiF, phiC, Lf);
+	with_nd(Lf.nd, [&](auto ND) { hipLaunchKernelGGL(k_prolong_add<ND>, dim3(nb), dim3(kThreads), 0, st, phiF, phiC, Lf); });
 	return check_launch("prolong_add");
 }
 
@@ -1899,9 +1897,7 @@ extern "C" int pinc_hip_mg_coarse(const double *rho, double *phi, int nLevels, c
 	a.hw3d = hw3d;
 	a.gs3d = gs3d;
 	hipStream_t st = (hipStream_t)stream;
-	if (nd == 3) hipLaunchKernelGGL(k_mg_coarse<3>, dim3(1), dim3(1024), 0, st, rho, phi, a);
-	else if (nd == 2) hipLaunchKernelGGL(k_mg_coarse<2>, dim3(1), dim3(1024), 0, st, rho, phi, a);
-	else hipLaunchKernelGGL(k_mg_coarse<1>, dim3(1), dim3(1024), 0, st, rho, phi, a);
+	with_nd(nd, [&](auto ND) { hipLaunchKernelGGL(k_mg_coarse<ND>, dim3(1), dim3(1024), 0, st, rho, phi, a); });
 	return check_launch("mg_coarse");
 }
 

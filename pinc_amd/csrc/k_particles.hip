@@ -3305,6 +3305,41 @@ __global__ __launch_bounds__(kThreads) void k_vel_assert(const double *__restric
 }  // namespace
 
 // =========================================================== C ABI ========
+// Every entry point marshals its arguments and launches one instance chosen
+// by with_nd; species_span and upto_nd (common.h) form the particle range and
+// the per-dimension pointers.
+
+// the classification thresholds from the host's thr[3 * nd] (lower, upper,
+// upper limit of each dimension); T is the number of true cells
+static Thr make_thr(const double *thr, int nd) {
+	Thr t;
+	for (int d = 0; d < 3; d++) {
+		t.lo[d] = d < nd ? thr[d] : 0;
+		t.up[d] = d < nd ? thr[nd + d] : 0;
+		t.hi[d] = d < nd ? thr[2 * nd + d] : 0;
+		t.T[d] = d < nd ? (int)(thr[2 * nd + d] - 1.0 + 0.5) : 1;
+	}
+	return t;
+}
+
+// the neighbour code of a particle that stays: digit 1 in every dimension
+static int flag_center(int nd) {
+	int center = 0;
+	for (int d = 0, p = 1; d < nd; d++, p *= 3) center += p;
+	return center;
+}
+
+// multi-block scan of counts[0, n) into offsets (a single workgroup takes
+// ~0.7 ms for 5e5 values); work: block sums[nsb] | block offsets[nsb + 1],
+// nsb = ceil(n / kScanBlock)
+static void scan_ints(const int *counts, long n, int *offsets, int *work, hipStream_t st) {
+	const long nsb = ceil_div(n, (long)kScanBlock);
+	int *bsum = work, *boff = work + nsb;
+	hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nsb), dim3(kThreads), 0, st, counts, n, bsum);
+	hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, boff, (int)nsb);
+	hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nsb), dim3(kThreads), 0, st, counts, n, boff, offsets);
+}
+
 extern "C" long pinc_hip_push_chunk(void) { return kPushChunk; }
 
 extern "C" int pinc_hip_push_xcd_of_chunks(long nBlocks, int *xcd) {
@@ -3313,40 +3348,31 @@ extern "C" int pinc_hip_push_xcd_of_chunks(long nBlocks, int *xcd) {
 }
 
 extern "C" int pinc_hip_deposit_ngp(pinc_pop_t pop, int s, pinc_geom_t g, double *rho, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = ceil_div(n, (long)kThreads);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	long nb = ceil_div(sp.n, (long)kThreads);
 	if (nb > 65536) nb = 65536;
 	hipStream_t st = (hipStream_t)stream;
-	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr, *x2 = g.nd > 2 ? pop.x[2] : nullptr;
-	if (g.nd == 3)
-		hipLaunchKernelGGL(k_deposit_ngp<3>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL(k_deposit_ngp<2>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
-	else
-		hipLaunchKernelGGL(k_deposit_ngp<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
+	const auto x = upto_nd(pop.x, g.nd);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_deposit_ngp<ND>, dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, sp.b0, sp.n, g, rho);
+	});
 	return check_launch("deposit (NGP)");
 }
 
 extern "C" int pinc_hip_accelerate_ngp(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es, double *kePartial,
                                        int *nBlocks, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
+	const Span sp = species_span(pop, s);
 	*nBlocks = 0;
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = ceil_div(n, (long)kAccChunk);
+	if (sp.n <= 0) return 0;
+	long nb = ceil_div(sp.n, (long)kAccChunk);
 	*nBlocks = (int)nb;
 	hipStream_t st = (hipStream_t)stream;
-	if (g.nd == 3)
-		hipLaunchKernelGGL(k_accel_ngp<3>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], pop.x[2], pop.v[0],
-		                   pop.v[1], pop.v[2], b0, n, g, Es, kePartial);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL(k_accel_ngp<2>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], nullptr, pop.v[0],
-		                   pop.v[1], nullptr, b0, n, g, Es, kePartial);
-	else
-		hipLaunchKernelGGL(k_accel_ngp<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], nullptr, nullptr, pop.v[0],
-		                   nullptr, nullptr, b0, n, g, Es, kePartial);
+	const auto x = upto_nd(pop.x, g.nd), v = upto_nd(pop.v, g.nd);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_accel_ngp<ND>, dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, v.a, v.b, v.c, sp.b0, sp.n,
+		                   g, Es, kePartial);
+	});
 	return check_launch("accelerate (NGP)");
 }
 
@@ -3361,18 +3387,14 @@ static int tsc_args_ok(const pinc_pop_t &pop, int s, const pinc_geom_t &g) {
 extern "C" int pinc_hip_deposit_tsc(pinc_pop_t pop, int s, pinc_geom_t g, double *rho, void *stream) {
 	if (!tsc_args_ok(pop, s, g) || !rho)
 		return set_error(hipErrorInvalidValue, "deposit (order 2): bad species, dimensions or null array");
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = chunk_blocks(b0, n, kDepChunk);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	long nb = chunk_blocks(sp.b0, sp.n, kDepChunk);
 	hipStream_t st = (hipStream_t)stream;
-	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr, *x2 = g.nd > 2 ? pop.x[2] : nullptr;
-	if (g.nd == 3)
-		hipLaunchKernelGGL(k_deposit_tsc<3>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL(k_deposit_tsc<2>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
-	else
-		hipLaunchKernelGGL(k_deposit_tsc<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, b0, n, g, rho);
+	const auto x = upto_nd(pop.x, g.nd);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_deposit_tsc<ND>, dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, sp.b0, sp.n, g, rho);
+	});
 	return check_launch("deposit (order 2)");
 }
 
@@ -3383,63 +3405,44 @@ extern "C" int pinc_hip_accelerate_tsc(pinc_pop_t pop, int s, pinc_geom_t g, con
 		return set_error(hipErrorInvalidValue, "accelerate (order 2): bad species, dimensions or null array");
 	for (int d = 0; d < g.nd; d++)
 		if (!pop.v[d]) return set_error(hipErrorInvalidValue, "accelerate (order 2): null velocity array");
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = ceil_div(n, (long)kAccChunk);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	long nb = ceil_div(sp.n, (long)kAccChunk);
 	*nBlocks = (int)nb;
 	hipStream_t st = (hipStream_t)stream;
-	if (g.nd == 3)
-		hipLaunchKernelGGL(k_accel_tsc<3>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], pop.x[2], pop.v[0],
-		                   pop.v[1], pop.v[2], b0, n, g, Es, kePartial);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL(k_accel_tsc<2>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], nullptr, pop.v[0],
-		                   pop.v[1], nullptr, b0, n, g, Es, kePartial);
-	else
-		hipLaunchKernelGGL(k_accel_tsc<1>, dim3(nb), dim3(kThreads), 0, st, pop.x[0], nullptr, nullptr, pop.v[0],
-		                   nullptr, nullptr, b0, n, g, Es, kePartial);
+	const auto x = upto_nd(pop.x, g.nd), v = upto_nd(pop.v, g.nd);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_accel_tsc<ND>, dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, v.a, v.b, v.c, sp.b0, sp.n,
+		                   g, Es, kePartial);
+	});
 	return check_launch("accelerate (order 2)");
 }
 
 extern "C" int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *errFlag, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long nb = ceil_div(n, (long)kThreads * 8);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	long nb = ceil_div(sp.n, (long)kThreads * 8);
 	if (nb > 16384) nb = 16384;
-	long b0 = pop.iStart[s];
-	hipLaunchKernelGGL(k_vel_assert, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, pop.v[0],
-	                   pop.nd > 1 ? pop.v[1] : nullptr, pop.nd > 2 ? pop.v[2] : nullptr, b0, n, pop.nd, maxVel,
-	                   errFlag);
+	const auto v = upto_nd(pop.v, pop.nd);
+	hipLaunchKernelGGL(k_vel_assert, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, v.a, v.b, v.c, sp.b0, sp.n,
+	                   pop.nd, maxVel, errFlag);
 	return check_launch("velocity assert");
 }
+
 extern "C" int pinc_hip_move_classify(pinc_pop_t pop, int s, int doMove, const double *thr,
                                       unsigned char *flags, int *chunkCount, double maxVel,
                                       int *errFlag, int wrapMask, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	Thr t;
-	int nd = pop.nd;
-	for (int d = 0; d < 3; d++) {
-		t.lo[d] = d < nd ? thr[d] : 0;
-		t.up[d] = d < nd ? thr[nd + d] : 0;
-		t.hi[d] = d < nd ? thr[2 * nd + d] : 0;
-		t.T[d] = d < nd ? (int)(thr[2 * nd + d] - 1.0 + 0.5) : 1;
-	}
-	int center = 0;
-	for (int d = 0, p = 1; d < nd; d++, p *= 3) center += p;
-	dim3 grid((unsigned)ceil_div(n, PINC_CHUNK));
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	const int nd = pop.nd;
+	const Thr t = make_thr(thr, nd);
+	const auto x = upto_nd(pop.x, nd, sp.b0), v = upto_nd(pop.v, nd, sp.b0);
+	dim3 grid((unsigned)ceil_div(sp.n, PINC_CHUNK));
 	hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_MC(ND)                                                                          \
-	hipLaunchKernelGGL(k_move_classify<ND>, grid, dim3(kThreads), 0, st, pop.x[0] + b0,        \
-	                   nd > 1 ? pop.x[1] + b0 : nullptr, nd > 2 ? pop.x[2] + b0 : nullptr,     \
-	                   pop.v[0] + b0, nd > 1 ? pop.v[1] + b0 : nullptr,                        \
-	                   nd > 2 ? pop.v[2] + b0 : nullptr, n, doMove, t, center, flags + b0,     \
-	                   chunkCount, maxVel, errFlag, wrapMask)
-	if (nd == 3) LAUNCH_MC(3);
-	else if (nd == 2) LAUNCH_MC(2);
-	else LAUNCH_MC(1);
-#undef LAUNCH_MC
+	with_nd(nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_move_classify<ND>, grid, dim3(kThreads), 0, st, x.a, x.b, x.c, v.a, v.b, v.c, sp.n, doMove,
+		                   t, flag_center(nd), flags + sp.b0, chunkCount, maxVel, errFlag, wrapMask);
+	});
 	return check_launch("move_classify");
 }
 
@@ -3456,23 +3459,16 @@ extern "C" int pinc_hip_extract(pinc_pop_t pop, int s, unsigned char *flags, int
                                 long *neCount, void *stream) {
 	(void)nNeighbors;
 	hipStream_t st = (hipStream_t)stream;
-	long n = pop.iStop[s] - pop.iStart[s];
-	long sb = pop.iStart[s];
+	const Span sp = species_span(pop, s);
+	const long n = sp.n, sb = sp.b0;
 	*nEmig = 0;
 	for (int q = 0; q < kMaxNe; q++) neCount[q] = 0;
 	if (n <= 0) return 0;
 	int nChunks = (int)ceil_div(n, PINC_CHUNK);
-	if (nChunks <= 4096 || !ws.scanWork) {
+	if (nChunks <= 4096 || !ws.scanWork)
 		hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, chunkCount, ws.chunkOffset, nChunks);
-	} else {
-		// multi-block scan (a single workgroup takes ~0.7 ms for 5e5 chunks)
-		long nsb = ceil_div(nChunks, (long)kScanBlock);
-		int *bsum = ws.scanWork, *boff = ws.scanWork + nsb;
-		hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nsb), dim3(kThreads), 0, st, chunkCount, (long)nChunks, bsum);
-		hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, boff, (int)nsb);
-		hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nsb), dim3(kThreads), 0, st, chunkCount, (long)nChunks, boff,
-		                   ws.chunkOffset);
-	}
+	else
+		scan_ints(chunkCount, nChunks, ws.chunkOffset, ws.scanWork, st);
 	int *hp = pinned_ints();
 	if (!hp) return set_error(hipErrorOutOfMemory, "extract: pinned host words");
 	hipError_t e = hipMemcpyAsync(hp, ws.chunkOffset + nChunks, sizeof(int), hipMemcpyDeviceToHost, st);
@@ -3532,20 +3528,15 @@ extern "C" int pinc_hip_import_rec(pinc_pop_t pop, int s, long dst, const double
 }
 
 extern "C" int pinc_hip_deposit(pinc_pop_t pop, int s, pinc_geom_t g, double *rho, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = chunk_blocks(b0, n, kDepChunk);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	long nb = chunk_blocks(sp.b0, sp.n, kDepChunk);
 	hipStream_t st = (hipStream_t)stream;
-	const double *x0 = pop.x[0];
-	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr;
-	const double *x2 = g.nd > 2 ? pop.x[2] : nullptr;
-	if (g.nd == 3)
-		hipLaunchKernelGGL((k_deposit_tiled<3, true>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, b0, n, g, rho);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL((k_deposit_tiled<2, false>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, b0, n, g, rho);
-	else
-		hipLaunchKernelGGL((k_deposit_tiled<1, false>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, b0, n, g, rho);
+	const auto x = upto_nd(pop.x, g.nd);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL((k_deposit_tiled<ND, ND == 3>), dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, sp.b0, sp.n,
+		                   g, rho);
+	});
 	return check_launch("deposit");
 }
 
@@ -3555,19 +3546,16 @@ extern "C" int pinc_hip_moments(pinc_pop_t pop, int s, pinc_geom_t g, const doub
 		return set_error(hipErrorInvalidValue, "moments: bad species, dimensions or null array");
 	for (int d = 0; d < g.nd; d++)
 		if (!pop.x[d] || !v[d]) return set_error(hipErrorInvalidValue, "moments: null particle array");
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = chunk_blocks(b0, n, kMomChunk);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	long nb = chunk_blocks(sp.b0, sp.n, kMomChunk);
 	hipStream_t st = (hipStream_t)stream;
-	const double *x1 = g.nd > 1 ? pop.x[1] : nullptr, *x2 = g.nd > 2 ? pop.x[2] : nullptr;
-	const double *v1 = g.nd > 1 ? v[1] : nullptr, *v2 = g.nd > 2 ? v[2] : nullptr;
-	if (g.nd == 3)
-		hipLaunchKernelGGL((k_moments<3>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL((k_moments<2>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
-	else
-		hipLaunchKernelGGL((k_moments<1>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], x1, x2, v[0], v1, v2, b0, n, g, momSlab);
+	const auto x = upto_nd(pop.x, g.nd);
+	const auto w = upto_nd(v, g.nd);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL((k_moments<ND>), dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, w.a, w.b, w.c, sp.b0, sp.n, g,
+		                   momSlab);
+	});
 	return check_launch("moments");
 }
 
@@ -3590,14 +3578,14 @@ extern "C" int pinc_hip_phase_hist(pinc_pop_t pop, int s, const double *const v[
 	if (na == 1 && spec.nbins[1] != 1) return set_error(hipErrorInvalidValue, "phase_hist: nbins[1] != 1 without a second axis");
 	if ((long)spec.nbins[0] * spec.nbins[1] > (1L << 24))
 		return set_error(hipErrorInvalidValue, "phase_hist: more than 2^24 bins");
-	const long b0 = pop.iStart[s], n = pop.iStop[s] - b0;
-	if (n <= 0) return 0;
-	const long nb = chunk_blocks(b0, n, kPhChunk);
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	const long nb = chunk_blocks(sp.b0, sp.n, kPhChunk);
 	hipStream_t st = (hipStream_t)stream;
 	if (na == 1)
-		hipLaunchKernelGGL((k_phase_hist<1>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], b0, n, spec, hist, outside);
+		hipLaunchKernelGGL((k_phase_hist<1>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], sp.b0, sp.n, spec, hist, outside);
 	else
-		hipLaunchKernelGGL((k_phase_hist<2>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], b0, n, spec, hist, outside);
+		hipLaunchKernelGGL((k_phase_hist<2>), dim3(nb), dim3(kThreads), 0, st, c[0], c[1], sp.b0, sp.n, spec, hist, outside);
 	return check_launch("phase_hist");
 }
 
@@ -3624,38 +3612,31 @@ extern "C" int pinc_hip_field_chain(const double *E, double *Es, long n, const d
 	return check_launch("field chain");
 }
 
+// k_accel's blocks take kAccChunk slots from the even index at or below b0
+// (chunk_blocks), so that its paired loads stay 16-byte aligned
 extern "C" int pinc_hip_accelerate(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es,
                                    double *kePartial, int *nBlocks, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
+	const Span sp = species_span(pop, s);
 	*nBlocks = 0;
-	if (n <= 0) return 0;
+	if (sp.n <= 0) return 0;
 	if (!Es) return set_error(hipErrorInvalidValue, "accelerate: null E");
-	long b0 = pop.iStart[s];
-	long nb = ceil_div(n + (b0 & 1L), (long)kAccChunk);
+	long nb = chunk_blocks(sp.b0, sp.n, kAccChunk);
 	*nBlocks = (int)nb;
 	hipStream_t st = (hipStream_t)stream;
-	double *x0 = pop.x[0], *x1 = pop.x[1], *x2 = pop.x[2];
-	double *v0 = pop.v[0], *v1 = pop.v[1], *v2 = pop.v[2];
-	if (g.nd == 3)
-		hipLaunchKernelGGL((k_accel<3, true, true>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, v0, v1, v2, b0, n,
-		                   g, Es, kePartial);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL((k_accel<2, false, true>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, v0, v1, v2, b0,
-		                   n, g, Es, kePartial);
-	else
-		hipLaunchKernelGGL((k_accel<1, false, true>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, v0, v1, v2, b0,
-		                   n, g, Es, kePartial);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL((k_accel<ND, ND == 3, true>), dim3(nb), dim3(kThreads), 0, st, pop.x[0], pop.x[1], pop.x[2],
+		                   pop.v[0], pop.v[1], pop.v[2], sp.b0, sp.n, g, Es, kePartial);
+	});
 	return check_launch("accelerate");
 }
 
 extern "C" int pinc_hip_boris(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es, const double *T,
                               const double *S, double *kePartial, int *nBlocks, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
+	const Span sp = species_span(pop, s);
 	*nBlocks = 0;
 	if (g.nd != 3 || pop.nd != 3) return set_error(hipErrorInvalidValue, "boris: 3-D only (puBoris3D1)");
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
-	long nb = ceil_div(n + (b0 & 1L), (long)kAccChunk);
+	if (sp.n <= 0) return 0;
+	long nb = chunk_blocks(sp.b0, sp.n, kAccChunk);
 	*nBlocks = (int)nb;
 	BorisRot rot;
 	for (int q = 0; q < 3; q++) {
@@ -3663,7 +3644,7 @@ extern "C" int pinc_hip_boris(pinc_pop_t pop, int s, pinc_geom_t g, const double
 		rot.S[q] = S[q];
 	}
 	hipLaunchKernelGGL((k_accel<3, true, true, true>), dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, pop.x[0],
-	                   pop.x[1], pop.x[2], pop.v[0], pop.v[1], pop.v[2], b0, n, g, Es, kePartial, rot);
+	                   pop.x[1], pop.x[2], pop.v[0], pop.v[1], pop.v[2], sp.b0, sp.n, g, Es, kePartial, rot);
 	return check_launch("boris");
 }
 
@@ -3752,73 +3733,61 @@ extern "C" int pinc_hip_sort_tiles(pinc_pop_t pop, pinc_pop_t out, int s, pinc_g
 	TileGeo tg = make_tile_geo(g, tileWidth, &nk);
 	long nsb = ceil_div(nk, (long)kScanBlock);
 	*nKeysOut = nk;
-	// work: counts[nk+1] | offsets[nk+1] | block sums[nsb] | block offsets[nsb+1]
+	// work: counts[nk+1] | offsets[nk+1] | scan_ints' work
 	long need = 2 * (nk + 1) + 2 * nsb + 1;
 	if (need > workCap || nk > 2147483647L) return set_error(hipErrorInvalidValue, "sort_tiles: work buffer too small");
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
-	if (n > 2147483647L) return set_error(hipErrorInvalidValue, "sort_tiles: species too large for int slots");
-	long b0 = pop.iStart[s];
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	if (sp.n > 2147483647L) return set_error(hipErrorInvalidValue, "sort_tiles: species too large for int slots");
 	hipStream_t st = (hipStream_t)stream;
-	int *counts = work, *offs = work + (nk + 1), *bsum = offs + (nk + 1), *boff = bsum + nsb;
+	int *counts = work, *offs = work + (nk + 1);
 	hipError_t e = hipMemsetAsync(counts, 0, (nk + 1) * sizeof(int), st);
 	if (e != hipSuccess) return set_error(e, "sort_tiles: memset");
-	long nb = ceil_div(n, (long)kThreads);
+	long nb = ceil_div(sp.n, (long)kThreads);
 	if (nb > 65536L * 8) nb = 65536L * 8;
-	int nd = g.nd;
-	const double *x0 = pop.x[0] + b0, *x1 = nd > 1 ? pop.x[1] + b0 : nullptr, *x2 = nd > 2 ? pop.x[2] + b0 : nullptr;
-	if (nd == 3) hipLaunchKernelGGL(k_sort_count<3>, dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, n, tg, counts);
-	else if (nd == 2) hipLaunchKernelGGL(k_sort_count<2>, dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, n, tg, counts);
-	else hipLaunchKernelGGL(k_sort_count<1>, dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, n, tg, counts);
-	hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nsb), dim3(kThreads), 0, st, counts, nk, bsum);
-	hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, boff, (int)nsb);
-	hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nsb), dim3(kThreads), 0, st, counts, nk, boff, offs);
-	if (nd == 3) hipLaunchKernelGGL(k_sort_scatter<3>, dim3(nb), dim3(kThreads), 0, st, pop, out, b0, n, tg, offs);
-	else if (nd == 2) hipLaunchKernelGGL(k_sort_scatter<2>, dim3(nb), dim3(kThreads), 0, st, pop, out, b0, n, tg, offs);
-	else hipLaunchKernelGGL(k_sort_scatter<1>, dim3(nb), dim3(kThreads), 0, st, pop, out, b0, n, tg, offs);
+	const auto x = upto_nd(pop.x, g.nd, sp.b0);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_sort_count<ND>, dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, sp.n, tg, counts);
+	});
+	scan_ints(counts, nk, offs, offs + (nk + 1), st);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_sort_scatter<ND>, dim3(nb), dim3(kThreads), 0, st, pop, out, sp.b0, sp.n, tg, offs);
+	});
 	return check_launch("sort_tiles");
 }
 
 extern "C" int pinc_hip_deposit_cells(pinc_pop_t pop, int s, pinc_geom_t g, int tileWidth, const int *offs,
                                       long nCell, double *rho, void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
-	if (n <= 0) return 0;
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
 	long nKeys = 0;
 	TileGeo tg = make_tile_geo(g, tileWidth, &nKeys);
-	long b0 = pop.iStart[s];
-	if (nCell > n) nCell = n;
+	if (nCell > sp.n) nCell = sp.n;
 	hipStream_t st = (hipStream_t)stream;
-	const double *x0 = pop.x[0] + b0;
-	const double *x1 = g.nd > 1 ? pop.x[1] + b0 : nullptr;
-	const double *x2 = g.nd > 2 ? pop.x[2] + b0 : nullptr;
+	const auto x = upto_nd(pop.x, g.nd, sp.b0);
 	unsigned nb = (unsigned)ceil_div(nKeys, (long)kThreads);
-	if (g.nd == 3)
-		hipLaunchKernelGGL((k_deposit_cells<3, true>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, nCell, offs, nKeys,
-		                   tg, g, rho);
-	else if (g.nd == 2)
-		hipLaunchKernelGGL((k_deposit_cells<2, false>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, nCell, offs,
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL((k_deposit_cells<ND, ND == 3>), dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, nCell, offs,
 		                   nKeys, tg, g, rho);
-	else
-		hipLaunchKernelGGL((k_deposit_cells<1, false>), dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, nCell, offs,
-		                   nKeys, tg, g, rho);
+	});
 	int rc = check_launch("deposit_cells");
-	if (rc || nCell >= n) return rc;
+	if (rc || nCell >= sp.n) return rc;
 	// particles appended since the sort (immigrants): generic deposit
 	pinc_pop_t tail = pop;
-	tail.iStart[s] = b0 + nCell;
+	tail.iStart[s] = sp.b0 + nCell;
 	return pinc_hip_deposit(tail, s, g, rho, stream);
 }
 
 extern "C" int pinc_hip_push(pinc_pop_t pop, int s, pinc_geom_t g, const pinc_push_t *args, int *nBlocks,
                              void *stream) {
-	long n = pop.iStop[s] - pop.iStart[s];
+	const Span sp = species_span(pop, s);
 	*nBlocks = 0;
-	if (n <= 0) return 0;
-	long b0 = pop.iStart[s];
+	if (sp.n <= 0) return 0;
+	const long b0 = sp.b0;
 	int nd = pop.nd;
 	if (nd != g.nd) return set_error(hipErrorInvalidValue, "push: population and grid dimensions differ");
 	const bool sort = args->cursor != nullptr;
-	if (sort && n > 2147483647L) return set_error(hipErrorInvalidValue, "push: species too large for int slots");
+	if (sort && sp.n > 2147483647L) return set_error(hipErrorInvalidValue, "push: species too large for int slots");
 	long nodes = 1;
 	for (int d = 0; d < nd; d++) nodes *= (d == nd - 1) ? (long)g.nloc + 2 : (long)g.T[d];
 	if (nodes * nd >= 2147483647L) return set_error(hipErrorInvalidValue, "push: grid too large for 32-bit offsets");
@@ -3828,17 +3797,13 @@ extern "C" int pinc_hip_push(pinc_pop_t pop, int s, pinc_geom_t g, const pinc_pu
 		a.xo[d] = d < nd ? args->xout[d] + b0 : nullptr;
 		a.vi[d] = d < nd ? pop.v[d] + b0 : nullptr;
 		a.vo[d] = d < nd ? args->vout[d] + b0 : nullptr;
-		a.thr.lo[d] = d < nd ? args->thr[d] : 0;
-		a.thr.up[d] = d < nd ? args->thr[nd + d] : 0;
-		a.thr.hi[d] = d < nd ? args->thr[2 * nd + d] : 0;
-		a.thr.T[d] = d < nd ? (int)(args->thr[2 * nd + d] - 1.0 + 0.5) : 1;
 	}
-	a.n = n;
+	a.thr = make_thr(args->thr, nd);
+	a.n = sp.n;
 	a.g = g;
 	a.Es = args->Es;
 	a.rho = args->rhoS;
-	a.center = 0;
-	for (int d = 0, p = 1; d < nd; d++, p *= 3) a.center += p;
+	a.center = flag_center(nd);
 	a.wrapMask = args->wrapMask;
 	a.maxVel = args->maxVel;
 	a.flags = args->flags + b0;
@@ -3870,25 +3835,27 @@ extern "C" int pinc_hip_push(pinc_pop_t pop, int s, pinc_geom_t g, const pinc_pu
 		if (a.objExt[d] >= 0 && (a.objLo[d] < 0 || (long)a.objLo[d] + a.objExt[d] >= (d == 0 ? a.objSy : d == 1 ? a.objSz / a.objSy
 		                                                                                             : a.objN / a.objSz)))
 			return set_error(hipErrorInvalidValue, "push: object box outside the node table");
-	unsigned nb = (unsigned)ceil_div(n, kPushChunk);
+	unsigned nb = (unsigned)ceil_div(sp.n, kPushChunk);
 	*nBlocks = (int)nb;
 	hipStream_t st = (hipStream_t)stream;
 	const bool kick = args->kick != 0;
 	if (kick && !args->Es) return set_error(hipErrorInvalidValue, "push: kick without E");
 	// a sorting push never counts (its brick counters use the count's LDS)
 	if (sort) a.cntNext = nullptr;
-#define LAUNCH_PUSH(ND, V3D, OBJ)                                                                                       \
-	do {                                                                                                                \
-		if (kick && sort) hipLaunchKernelGGL((k_push<ND, V3D, true, true, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a); \
-		else if (kick) hipLaunchKernelGGL((k_push<ND, V3D, true, false, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);   \
-		else if (sort) hipLaunchKernelGGL((k_push<ND, V3D, false, true, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);   \
-		else hipLaunchKernelGGL((k_push<ND, V3D, false, false, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);            \
-	} while (0)
-	if (nd == 3 && a.objIn) LAUNCH_PUSH(3, true, true);
-	else if (nd == 3) LAUNCH_PUSH(3, true, false);
-	else if (nd == 2) LAUNCH_PUSH(2, false, false);
-	else LAUNCH_PUSH(1, false, false);
-#undef LAUNCH_PUSH
+	auto launch = [&](auto ND, auto OBJ) {
+		constexpr bool V3D = ND == 3;
+		if (kick && sort) hipLaunchKernelGGL((k_push<ND, V3D, true, true, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);
+		else if (kick) hipLaunchKernelGGL((k_push<ND, V3D, true, false, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);
+		else if (sort) hipLaunchKernelGGL((k_push<ND, V3D, false, true, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);
+		else hipLaunchKernelGGL((k_push<ND, V3D, false, false, OBJ>), dim3(nb), dim3(kPushThreads), 0, st, a);
+	};
+	// (the object test exists in the 3-D instances only)
+	with_nd(nd, [&](auto ND) {
+		if constexpr (ND == 3) {
+			if (a.objIn) return launch(ND, std::true_type{});
+		}
+		launch(ND, std::false_type{});
+	});
 	return check_launch("push");
 }
 
@@ -3907,29 +3874,21 @@ extern "C" int pinc_hip_count_keys(pinc_pop_t pop, int s, long first, pinc_geom_
 	TileGeo tg = make_tile_geo(g, tileWidth, &nk);
 	long nb = ceil_div(n, (long)kThreads);
 	if (nb > 65536L * 8) nb = 65536L * 8;
-	int nd = g.nd;
-	const double *x0 = pop.x[0] + b0, *x1 = nd > 1 ? pop.x[1] + b0 : nullptr, *x2 = nd > 2 ? pop.x[2] + b0 : nullptr;
-	const double *v0 = pop.v[0] + b0, *v1 = nd > 1 ? pop.v[1] + b0 : nullptr, *v2 = nd > 2 ? pop.v[2] + b0 : nullptr;
+	const auto x = upto_nd(pop.x, g.nd, b0), v = upto_nd(pop.v, g.nd, b0);
 	hipStream_t st = (hipStream_t)stream;
-	if (nd == 3)
-		hipLaunchKernelGGL(k_count_bricks<3>, dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, v0, v1, v2, n, tg, counts);
-	else if (nd == 2)
-		hipLaunchKernelGGL(k_count_bricks<2>, dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, v0, v1, v2, n, tg, counts);
-	else hipLaunchKernelGGL(k_count_bricks<1>, dim3(nb), dim3(kThreads), 0, st, x0, x1, x2, v0, v1, v2, n, tg, counts);
+	with_nd(g.nd, [&](auto ND) {
+		hipLaunchKernelGGL(k_count_bricks<ND>, dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, v.a, v.b, v.c, n, tg,
+		                   counts);
+	});
 	return check_launch("count_keys");
 }
 
 extern "C" int pinc_hip_scan_keys(const int *counts, long nKeys, int *offsets, int *work, void *stream) {
-	long nsb = ceil_div(nKeys, (long)kScanBlock);
-	if (nsb > 1024L * 1024L) return set_error(hipErrorInvalidValue, "scan_keys: too many keys");
-	int *bsum = work, *boff = work + nsb;
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nsb), dim3(kThreads), 0, st, counts, nKeys, bsum);
-	hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, bsum, boff, (int)nsb);
-	hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nsb), dim3(kThreads), 0, st, counts, nKeys, boff, offsets);
+	if (ceil_div(nKeys, (long)kScanBlock) > 1024L * 1024L)
+		return set_error(hipErrorInvalidValue, "scan_keys: too many keys");
+	scan_ints(counts, nKeys, offsets, work, (hipStream_t)stream);
 	return check_launch("scan_keys");
 }
-
 
 extern "C" int pinc_hip_rho_combine(double *rho, const double *const *acc, const double *charge, int ns, long n,
                                     void *stream) {

@@ -1009,17 +1009,53 @@ void puMigrate(Population *pop, MpiInfo *m, Grid *grid) {
 }
 
 /* ------------------------------------------------------------- deposit -- */
-/* gZero; per species gMul(1/q), scatter, gMul(q) (pusher.c:512-572): the
- * consecutive gMul(q_{s-1}), gMul(1/q_s) become one two-rounding pass. */
-static void distr(const Population *pop, Grid *rho) {
+/* The deposit of every species into d[0, n): gZero; per species gMul(1/q),
+ * scatter, gMul(q) (pusher.c:512-572, 640-668), where the consecutive
+ * gMul(q_{s-1}), gMul(1/q_s) become one two-rounding pass.  order picks the
+ * scatter: 0 one unit at the nearest node, 1 CIC, 2 the quadratic-spline
+ * weights on the 3^nd nodes around the nearest one.  op1: the deposit of the
+ * order-1 operator itself, which goes by the cells of a valid tile sort and
+ * carries the deposit probe. */
+static void deposit_chain(const Population *pop, pinc_geom_t geo, int order, double *d, long n, int op1) {
+	const PincDevPop *dv = pop->dev;
+	pinc_check(pinc_hip_zero(d, n, g_pinc.stream), "distr zero");
+	pinc_pop_t p = pinc_devpop(pop);
+	for (int s = 0; s < pop->nSpecies; s++) {
+		if (s > 0)
+			pinc_check(pinc_hip_scale2(d, n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream), "distr scale");
+		int slot = op1 ? pinc_probe_begin(PINC_PROBE_DEPOSIT) : -1;
+		switch (order) {
+		case 0:
+			pinc_check(pinc_hip_deposit_ngp(p, s, geo, d, g_pinc.stream), "deposit (NGP)");
+			break;
+		case 2:
+			pinc_check(pinc_hip_deposit_tsc(p, s, geo, d, g_pinc.stream), "deposit (order 2)");
+			break;
+		default:
+			if (op1 && dv->tiled && dv->cellValid[s] >= 0)
+				pinc_check(pinc_hip_deposit_cells(p, s, geo, dv->tileWidth, dv->sortWork[s] + (dv->sortKeys + 1),
+				                                  dv->cellValid[s], d, g_pinc.stream),
+				           "deposit (cells)");
+			else
+				pinc_check(pinc_hip_deposit(p, s, geo, d, g_pinc.stream), "deposit");
+		}
+		/* read pos (8 B per dim per particle) + write rho (8 B per node) */
+		pinc_probe_end(PINC_PROBE_DEPOSIT, slot, 8.0 * pop->nDims * (pop->iStop[s] - pop->iStart[s]) + 8.0 * n);
+	}
+	pinc_check(pinc_hip_scale(d, n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "distr scale");
+}
+
+/* puDistr3D1/ND1 (order 1), puDistrND0 and puDistrND2.  Only order 1 uses a
+ * fused push's deposit, which is CIC. */
+static void distr(const Population *pop, Grid *rho, int order) {
 	pinc_pop_flush_host(pop);
 	pinc_phase_begin(3);
 	PincDevGrid *g = rho->dev;
 	g->depPop = pop;
-	g->depOrder = 1;
+	g->depOrder = order;
 	g->folds = 0;
 	PincDevPop *dvp = pop->dev;
-	if (dvp->depValid && dvp->depExtracted && dvp->rhoN == g->n) {
+	if (order == 1 && dvp->depValid && dvp->depExtracted && dvp->rhoN == g->n) {
 		/* fused push: the particles that stayed are in rhoS; add the ones
 		 * imported since (the tail of each species), then combine */
 		for (int s = 0; s < pop->nSpecies; s++) {
@@ -1032,80 +1068,16 @@ static void distr(const Population *pop, Grid *rho) {
 		                                g_pinc.stream),
 		           "rho combine");
 		dvp->depValid = dvp->depExtracted = 0;
-		g->ghostsValid = 0;
-		pinc_phase_end(3);
-		return;
+	} else {
+		if (order != 1) dvp->depValid = dvp->depExtracted = 0;
+		deposit_chain(pop, g->geom, order, g->d, g->n, order == 1);
 	}
-	pinc_check(pinc_hip_zero(g->d, g->n, g_pinc.stream), "distr zero");
-	pinc_pop_t p = pinc_devpop(pop);
-	for (int s = 0; s < pop->nSpecies; s++) {
-		if (s > 0)
-			pinc_check(pinc_hip_scale2(g->d, g->n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream),
-			           "distr scale");
-		int slot = pinc_probe_begin(PINC_PROBE_DEPOSIT);
-		PincDevPop *dv = pop->dev;
-		if (dv->tiled && dv->cellValid[s] >= 0)
-			pinc_check(pinc_hip_deposit_cells(p, s, g->geom, dv->tileWidth, dv->sortWork[s] + (dv->sortKeys + 1),
-			                                  dv->cellValid[s], g->d, g_pinc.stream),
-			           "deposit (cells)");
-		else
-			pinc_check(pinc_hip_deposit(p, s, g->geom, g->d, g_pinc.stream), "deposit");
-		/* read pos (8 B per dim per particle) + write rho (8 B per node) */
-		pinc_probe_end(PINC_PROBE_DEPOSIT, slot,
-		               8.0 * pop->nDims * (pop->iStop[s] - pop->iStart[s]) + 8.0 * g->n);
-	}
-	pinc_check(pinc_hip_scale(g->d, g->n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "distr scale");
 	g->ghostsValid = 0;
 	pinc_phase_end(3);
 }
 
-/* gZero; per species gMul(1/q), one unit per particle at its nearest node,
- * gMul(q) (puDistrND0, pusher.c:640-668).  A fused push's CIC deposit is not
- * used. */
-void puDistrND0(const Population *pop, Grid *rho) {
-	pinc_pop_flush_host(pop);
-	pinc_phase_begin(3);
-	PincDevGrid *g = rho->dev;
-	g->depPop = pop;
-	g->depOrder = 0;
-	g->folds = 0;
-	pop->dev->depValid = pop->dev->depExtracted = 0;
-	pinc_check(pinc_hip_zero(g->d, g->n, g_pinc.stream), "distr zero");
-	pinc_pop_t p = pinc_devpop(pop);
-	for (int s = 0; s < pop->nSpecies; s++) {
-		if (s > 0)
-			pinc_check(pinc_hip_scale2(g->d, g->n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream),
-			           "distr scale");
-		pinc_check(pinc_hip_deposit_ngp(p, s, g->geom, g->d, g_pinc.stream), "deposit (NGP)");
-	}
-	pinc_check(pinc_hip_scale(g->d, g->n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "distr scale");
-	g->ghostsValid = 0;
-	pinc_phase_end(3);
-}
-
-/* gZero; per species gMul(1/q), the quadratic-spline weights of every
- * particle on the 3^nd nodes around its nearest one, gMul(q): puDistrND0's
- * chain with pinc_hip_deposit_tsc.  A fused push's CIC deposit is not used. */
-void puDistrND2(const Population *pop, Grid *rho) {
-	pinc_pop_flush_host(pop);
-	pinc_phase_begin(3);
-	PincDevGrid *g = rho->dev;
-	g->depPop = pop;
-	g->depOrder = 2;
-	g->folds = 0;
-	pop->dev->depValid = pop->dev->depExtracted = 0;
-	pinc_check(pinc_hip_zero(g->d, g->n, g_pinc.stream), "distr zero");
-	pinc_pop_t p = pinc_devpop(pop);
-	for (int s = 0; s < pop->nSpecies; s++) {
-		if (s > 0)
-			pinc_check(pinc_hip_scale2(g->d, g->n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream),
-			           "distr scale");
-		pinc_check(pinc_hip_deposit_tsc(p, s, g->geom, g->d, g_pinc.stream), "deposit (order 2)");
-	}
-	pinc_check(pinc_hip_scale(g->d, g->n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "distr scale");
-	g->ghostsValid = 0;
-	pinc_phase_end(3);
-}
+void puDistrND0(const Population *pop, Grid *rho) { distr(pop, rho, 0); }
+void puDistrND2(const Population *pop, Grid *rho) { distr(pop, rho, 2); }
 
 /* main.c:226 and :232 both call gHaloOp(addSlice, rho, FROMHALO) on one
  * deposit; ghost values are not cleared in between, so a
@@ -1120,17 +1092,7 @@ void pinc_literal_second_fold(const Population *pop, Grid *rho, int order) {
 	pinc_geom_t geo = g->geom;
 	geo.literal = 2;
 	if (!g->lit) pinc_check(pinc_hip_malloc((void **)&g->lit, g->n * sizeof(double)), "second fold scratch");
-	pinc_check(pinc_hip_zero(g->lit, g->n, g_pinc.stream), "second fold");
-	pinc_pop_t p = pinc_devpop(pop);
-	for (int s = 0; s < pop->nSpecies; s++) {
-		if (s > 0)
-			pinc_check(pinc_hip_scale2(g->lit, g->n, pop->charge[s - 1], 1.0 / pop->charge[s], g_pinc.stream),
-			           "second fold scale");
-		if (order == 0) pinc_check(pinc_hip_deposit_ngp(p, s, geo, g->lit, g_pinc.stream), "second fold (NGP)");
-		else if (order == 2) pinc_check(pinc_hip_deposit_tsc(p, s, geo, g->lit, g_pinc.stream), "second fold (order 2)");
-		else pinc_check(pinc_hip_deposit(p, s, geo, g->lit, g_pinc.stream), "second fold");
-	}
-	pinc_check(pinc_hip_scale(g->lit, g->n, pop->charge[pop->nSpecies - 1], g_pinc.stream), "second fold scale");
+	deposit_chain(pop, geo, order, g->lit, g->n, 0);
 	pinc_check(pinc_hip_add(g->d, g->lit, g->n, g_pinc.stream), "second fold add");
 }
 
@@ -1272,55 +1234,52 @@ void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *m
 	free(sum);
 }
 
-void puDistr3D1(const Population *pop, Grid *rho) { distr(pop, rho); }
-void puDistrND1(const Population *pop, Grid *rho) { distr(pop, rho); }
+void puDistr3D1(const Population *pop, Grid *rho) { distr(pop, rho, 1); }
+void puDistrND1(const Population *pop, Grid *rho) { distr(pop, rho, 1); }
 
 /* ----------------------------------------------------------- accelerate -- */
-static void acc(Population *pop, Grid *E, int ke) {
+/* The accelerate that is not fused with the move: per species E as rescaled
+ * for it, the kick, the sum of the kick's block partials into
+ * PINC_SLOT(16 + s); with ke the sums are read back into kinEnergy.  kick is
+ * the weighting order (0 nearest node, pusher.c:310-353; 1 CIC; 2 quadratic
+ * spline) or KICK_BORIS (half kick, rotation by T and S, 3 values per species,
+ * half kick).  Orders 1 and Boris carry the accelerate probe.  who names the
+ * operator that cannot follow a fused puAcc whose puMove is still pending
+ * (NULL: puAcc*1 itself, whose unfused branch never meets one). */
+enum { KICK_BORIS = 3 };
+
+static void kick_chain(Population *pop, Grid *E, int kick, const double *T, const double *S, int ke, const char *who) {
 	pinc_pop_flush_host(pop);
 	pinc_phase_begin(6);
 	PincDevPop *dv = pop->dev;
-	if (dv->fused) {
-		/* kick now; the drift of the next puMove, its classification and its
-		 * deposit ride along (positions to altX, swapped in by puMove) */
-		if (!dv->sorted) maybe_sort(pop);
-		dv->pending = 0;
-		dv->pendingSorted = push_all(pop, E, dv->altX);
-		for (int s = 0; s < PINC_MAX_SPECIES; s++) dv->vKicked[s] = 0;
-		pinc_pending_register(pop);
-		dv->pending = 1;
-		dv->pendingE = E;
-		dv->pendingESerial = E->dev->serial;
-		dv->pendingEGen = E->dev->gen;
-		dv->flagsValid = 0;
-		if (ke && dv->cntPending) {
-			/* the sums come with the sort counters (push_all): kinEnergy is
-			 * filled when they are taken in (pinc_pop_settle: pSumKinEnergy,
-			 * pWriteEnergy, the next push or extraction) */
-			dv->keDeferred = 1;
-		} else if (ke) {
-			double sums[PINC_MAX_SPECIES];
-			pinc_check(pinc_hip_d2h(sums, PINC_SLOT(16), pop->nSpecies * sizeof(double), g_pinc.stream), "ke readback");
-			for (int s = 0; s < pop->nSpecies; s++) pop->kinEnergy[s] = sums[s] * (0.5 * pop->mass[s]);
-		}
-		pinc_phase_end(6);
-		return;
-	}
+	if (who && dv->pending) msg(ERROR, "%s after a fused puAcc without its puMove", who);
 	pinc_pop_t p = pinc_devpop(pop);
-	int ns = pop->nSpecies;
+	const int ns = pop->nSpecies, probed = kick == 1 || kick == KICK_BORIS;
+	PincDevGrid *eg = E->dev;
+	if (!eg->scaled) pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
 	for (int s = 0; s < ns; s++) {
 		int nb = 0;
-		PincDevGrid *eg = E->dev;
-		if (!eg->scaled)
-			pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
-		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream),
-		           "E chain");
-		int slot = pinc_probe_begin(PINC_PROBE_ACCEL);
-		pinc_check(pinc_hip_accelerate(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
-		           "accelerate");
+		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream), "E chain");
+		int slot = probed ? pinc_probe_begin(PINC_PROBE_ACCEL) : -1;
+		switch (kick) {
+		case 0:
+			pinc_check(pinc_hip_accelerate_ngp(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
+			           "accelerate (NGP)");
+			break;
+		case 2:
+			pinc_check(pinc_hip_accelerate_tsc(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
+			           "accelerate (order 2)");
+			break;
+		case KICK_BORIS:
+			pinc_check(pinc_hip_boris(p, s, eg->geom, eg->scaled, T + 3 * s, S + 3 * s, dv->kePartial, &nb,
+			                          g_pinc.stream),
+			           "boris");
+			break;
+		default:
+			pinc_check(pinc_hip_accelerate(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream), "accelerate");
+		}
 		/* read pos+vel, write vel (72 B per 3-D particle) + read E once */
-		pinc_probe_end(PINC_PROBE_ACCEL, slot,
-		               24.0 * pop->nDims * (pop->iStop[s] - pop->iStart[s]) + 8.0 * E->dev->n);
+		pinc_probe_end(PINC_PROBE_ACCEL, slot, 24.0 * pop->nDims * (pop->iStop[s] - pop->iStart[s]) + 8.0 * eg->n);
 		if (nb > 0) pinc_check(pinc_hip_sum(dv->kePartial, nb, g_pinc.dScratch, PINC_SLOT(16 + s), g_pinc.stream), "ke");
 		else pinc_check(pinc_hip_memset(PINC_SLOT(16 + s), 0, sizeof(double), g_pinc.stream), "ke");
 	}
@@ -1332,90 +1291,49 @@ static void acc(Population *pop, Grid *E, int ke) {
 	pinc_phase_end(6);
 }
 
-/* per species: E as rescaled for s, half kick, rotation, half kick, KE */
-static void boris(Population *pop, Grid *E, const double *T, const double *S, int ke) {
+static void acc(Population *pop, Grid *E, int ke) {
+	PincDevPop *dv = pop->dev;
+	if (!dv->fused) {
+		kick_chain(pop, E, 1, NULL, NULL, ke, NULL);
+		return;
+	}
 	pinc_pop_flush_host(pop);
 	pinc_phase_begin(6);
-	PincDevPop *dv = pop->dev;
-	if (dv->pending) msg(ERROR, "Boris push after a fused puAcc without its puMove");
-	pinc_pop_t p = pinc_devpop(pop);
-	int ns = pop->nSpecies;
-	for (int s = 0; s < ns; s++) {
-		int nb = 0;
-		PincDevGrid *eg = E->dev;
-		if (!eg->scaled)
-			pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
-		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream),
-		           "E chain");
-		int slot = pinc_probe_begin(PINC_PROBE_ACCEL);
-		pinc_check(pinc_hip_boris(p, s, eg->geom, eg->scaled, T + 3 * s, S + 3 * s, dv->kePartial, &nb,
-		                          g_pinc.stream),
-		           "boris");
-		pinc_probe_end(PINC_PROBE_ACCEL, slot,
-		               24.0 * pop->nDims * (pop->iStop[s] - pop->iStart[s]) + 8.0 * E->dev->n);
-		if (nb > 0) pinc_check(pinc_hip_sum(dv->kePartial, nb, g_pinc.dScratch, PINC_SLOT(16 + s), g_pinc.stream), "ke");
-		else pinc_check(pinc_hip_memset(PINC_SLOT(16 + s), 0, sizeof(double), g_pinc.stream), "ke");
-	}
-	if (ke) {
+	/* kick now; the drift of the next puMove, its classification and its
+	 * deposit ride along (positions to altX, swapped in by puMove) */
+	if (!dv->sorted) maybe_sort(pop);
+	dv->pending = 0;
+	dv->pendingSorted = push_all(pop, E, dv->altX);
+	for (int s = 0; s < PINC_MAX_SPECIES; s++) dv->vKicked[s] = 0;
+	pinc_pending_register(pop);
+	dv->pending = 1;
+	dv->pendingE = E;
+	dv->pendingESerial = E->dev->serial;
+	dv->pendingEGen = E->dev->gen;
+	dv->flagsValid = 0;
+	if (ke && dv->cntPending) {
+		/* the sums come with the sort counters (push_all): kinEnergy is
+		 * filled when they are taken in (pinc_pop_settle: pSumKinEnergy,
+		 * pWriteEnergy, the next push or extraction) */
+		dv->keDeferred = 1;
+	} else if (ke) {
 		double sums[PINC_MAX_SPECIES];
-		pinc_check(pinc_hip_d2h(sums, PINC_SLOT(16), ns * sizeof(double), g_pinc.stream), "ke readback");
-		for (int s = 0; s < ns; s++) pop->kinEnergy[s] = sums[s] * (0.5 * pop->mass[s]);
+		pinc_check(pinc_hip_d2h(sums, PINC_SLOT(16), pop->nSpecies * sizeof(double), g_pinc.stream), "ke readback");
+		for (int s = 0; s < pop->nSpecies; s++) pop->kinEnergy[s] = sums[s] * (0.5 * pop->mass[s]);
 	}
 	pinc_phase_end(6);
+}
+
+static void boris(Population *pop, Grid *E, const double *T, const double *S, int ke) {
+	kick_chain(pop, E, KICK_BORIS, T, S, ke, "Boris push");
 }
 
 void puBoris3D1(Population *pop, Grid *E, const double *T, const double *S) { boris(pop, E, T, S, 0); }
 void puBoris3D1KE(Population *pop, Grid *E, const double *T, const double *S) { boris(pop, E, T, S, 1); }
 
-/* puAccND0KE (pusher.c:310-353): per species E as rescaled for it, v += E at
- * the nearest node, KE.  Not fused: the next puMove moves on its own. */
-void puAccND0KE(Population *pop, Grid *E) {
-	pinc_pop_flush_host(pop);
-	pinc_phase_begin(6);
-	PincDevPop *dv = pop->dev;
-	if (dv->pending) msg(ERROR, "puAccND0KE after a fused puAcc without its puMove");
-	pinc_pop_t p = pinc_devpop(pop);
-	int ns = pop->nSpecies;
-	PincDevGrid *eg = E->dev;
-	if (!eg->scaled) pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
-	for (int s = 0; s < ns; s++) {
-		int nb = 0;
-		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream), "E chain");
-		pinc_check(pinc_hip_accelerate_ngp(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
-		           "accelerate (NGP)");
-		if (nb > 0) pinc_check(pinc_hip_sum(dv->kePartial, nb, g_pinc.dScratch, PINC_SLOT(16 + s), g_pinc.stream), "ke");
-		else pinc_check(pinc_hip_memset(PINC_SLOT(16 + s), 0, sizeof(double), g_pinc.stream), "ke");
-	}
-	double sums[PINC_MAX_SPECIES];
-	pinc_check(pinc_hip_d2h(sums, PINC_SLOT(16), ns * sizeof(double), g_pinc.stream), "ke readback");
-	for (int s = 0; s < ns; s++) pop->kinEnergy[s] = sums[s] * (0.5 * pop->mass[s]);
-	pinc_phase_end(6);
-}
-
-/* puAccND2KE: puAccND0KE's sequence with the quadratic-spline gather
- * (pinc_hip_accelerate_tsc).  Not fused: the next puMove moves on its own. */
-void puAccND2KE(Population *pop, Grid *E) {
-	pinc_pop_flush_host(pop);
-	pinc_phase_begin(6);
-	PincDevPop *dv = pop->dev;
-	if (dv->pending) msg(ERROR, "puAccND2KE after a fused puAcc without its puMove");
-	pinc_pop_t p = pinc_devpop(pop);
-	int ns = pop->nSpecies;
-	PincDevGrid *eg = E->dev;
-	if (!eg->scaled) pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
-	for (int s = 0; s < ns; s++) {
-		int nb = 0;
-		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream), "E chain");
-		pinc_check(pinc_hip_accelerate_tsc(p, s, eg->geom, eg->scaled, dv->kePartial, &nb, g_pinc.stream),
-		           "accelerate (order 2)");
-		if (nb > 0) pinc_check(pinc_hip_sum(dv->kePartial, nb, g_pinc.dScratch, PINC_SLOT(16 + s), g_pinc.stream), "ke");
-		else pinc_check(pinc_hip_memset(PINC_SLOT(16 + s), 0, sizeof(double), g_pinc.stream), "ke");
-	}
-	double sums[PINC_MAX_SPECIES];
-	pinc_check(pinc_hip_d2h(sums, PINC_SLOT(16), ns * sizeof(double), g_pinc.stream), "ke readback");
-	for (int s = 0; s < ns; s++) pop->kinEnergy[s] = sums[s] * (0.5 * pop->mass[s]);
-	pinc_phase_end(6);
-}
+/* not fused: the next puMove moves on its own */
+void puAccND0KE(Population *pop, Grid *E) { kick_chain(pop, E, 0, NULL, NULL, 1, "puAccND0KE"); }
+void puAccND2KE(Population *pop, Grid *E) { kick_chain(pop, E, 2, NULL, NULL, 1, "puAccND2KE"); }
 
 void puAcc3D1(Population *pop, Grid *E) { acc(pop, E, 0); }
 void puAcc3D1KE(Population *pop, Grid *E) { acc(pop, E, 1); }

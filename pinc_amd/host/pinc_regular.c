@@ -487,7 +487,8 @@ int pinc_sim_op(PincSim *S, const char *op) {
 	else if (!strcmp(op, "distr")) {
 		S->distr(S->pop, S->rho);
 		gHaloOp((funPtr)addSlice, S->rho, S->mpi, FROMHALO);
-	} else if (!strcmp(op, "solve")) S->solve(S->solver, S->rho, S->phi, S->mpi);
+	} else if (!strcmp(op, "fold_rho")) gHaloOp((funPtr)addSlice, S->rho, S->mpi, FROMHALO); /* main.c:232 */
+	else if (!strcmp(op, "solve")) S->solve(S->solver, S->rho, S->phi, S->mpi);
 	else if (!strcmp(op, "efield")) {
 		gHaloOp((funPtr)setSlice, S->phi, S->mpi, TOHALO);
 		gFinDiff1st(S->phi, S->E);

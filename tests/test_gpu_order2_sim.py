@@ -16,6 +16,7 @@ import socket
 import subprocess
 import sys
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -132,6 +133,41 @@ def test_deposit_and_gather_against_the_restatement(built):
             lim = (27 + 8) * EPS * mag + EPS * np.abs(v)
             print(f"species {sp}: velocity error / bound {float(np.max(err / lim)):.3f}")
             assert np.all(err <= lim)
+
+
+def second_fold(pos):
+    """one species' true nodes after main.c:226 and :232 on a deposit made
+    without the literal factor: plain folded (ghost planes kept), plus the
+    literal-2 weights, folded once more (test_order2_ref_cpu's
+    test_literal_factors shows that this is literal 1 folded twice)"""
+    plain, lit2 = (O.slab(O.deposit(pos, S3, literal), S3) for literal in (0, 2))
+
+    def both(a, b):
+        a = a.copy()
+        a[S3[2]] += a[0]
+        a[1] += a[S3[2] + 1]
+        return O.fold(a + b, S3[2])
+    return SimpleNamespace(M=both(plain.M, lit2.M), A=both(plain.A, lit2.A), k=both(plain.k, lit2.k))
+
+
+def test_second_fold_against_the_restatement(built):
+    """op fold_rho after op distr is main.c:232's second FROMHALO add on one
+    order-2 deposit: pinc_literal_second_fold adds the literal-2 weights with
+    the deposit's species chain, then the planes fold again.  The deposit's
+    bound: the second fold's additions are among the k - 1 of its k terms, the
+    literal factor (1, 3, 7, doubled) is the rounding the kernel bound counts."""
+    with sim(order2(config("cold3d"))) as s:
+        s.init()
+        q, _ = s.species()
+        pos = species_positions(3000)
+        for sp in range(2):
+            s.set_particles(sp, pos[sp], np.zeros_like(pos[sp]))
+        s.op("distr")
+        s.op("fold_rho")
+        rho = s.grid(0)[1:-1, 1:-1, 1:-1, 0]
+    ref = O.charge_chain([second_fold(p) for p in pos], q)
+    assert np.any(ref.M != O.charge_chain([O.folded(O.slab(O.deposit(p, S3), S3), S3[2]) for p in pos], q).M)
+    check(rho, ref, "rho after the second fold")
 
 
 def _port():
