@@ -88,6 +88,9 @@ extern "C" int pinc_hip_fft_create(pinc_fft_t **out, int nd, const int *T, void 
 	(void)stream;
 	*out = nullptr;
 	if (nd < 1 || nd > 3) return set_error(hipErrorInvalidValue, "fft_create: nDims");
+	// every rejection comes before rocfft_setup and the plan count: from
+	// the count on, a failure leaves through pinc_hip_fft_destroy
+	if (T[0] % 2) return set_error(hipErrorInvalidValue, "fft_create: x size must be even");
 	if (!g_rocfft_ready) {
 		if (int rc = fft_error(rocfft_setup(), "rocfft_setup")) return rc;
 		g_rocfft_ready = true;
@@ -99,10 +102,6 @@ extern "C" int pinc_hip_fft_create(pinc_fft_t **out, int nd, const int *T, void 
 	for (int d = 0; d < 3; d++) {
 		f->T[d] = d < nd ? T[d] : 1;
 		f->nReal *= f->T[d];
-	}
-	if (f->T[0] % 2) {
-		free(f);
-		return set_error(hipErrorInvalidValue, "fft_create: x size must be even");
 	}
 	f->nSpec = f->nReal / f->T[0] * (f->T[0] / 2 + 1);
 	size_t len[3] = {(size_t)f->T[0], (size_t)f->T[1], (size_t)f->T[2]};  // fastest first
