@@ -269,6 +269,42 @@ typedef struct {
 	double lo[2], hi[2];
 } PhaseSpec;
 void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *mpiInfo, double *hist, double *outside);
+/* Monte Carlo collisions with a uniform neutral background (an extension: the
+ * reference has no collision module; the rule at pinc_hip_collide,
+ * include/pinc_hip.h): elastic scattering and charge exchange, every particle
+ * tested every step.  The ini's [collisions] section, all in code units
+ * (lengths in grid:stepSize[0], times in steps), read after uAlloc has run:
+ *   elasticNu, cexNu        rate per step, one value per species
+ *   elasticSigma, cexSigma  n_n sigma per unit of path, one value per species
+ *   neutralMass             in the units of population:mass as the input gives
+ *                           it (required when an elastic rate is set)
+ *   neutralVth              thermal speed per component (default 0)
+ *   neutralDrift            nDims values (default 0)
+ *   seed                    of the draws (default 0)
+ * uAlloc takes the neutral's share of each pair mass, b = m_n / (m_s + m_n),
+ * from the input's masses before it rewrites them and keeps it in the
+ * dictionary as collisions:neutralMassFraction, which mccAlloc reads (on a
+ * dictionary uAlloc has not seen, mccAlloc forms b from the masses as they
+ * stand); that key is the library's own and is msg(ERROR) in an input, as is
+ * any other key of the section that is none of the above.
+ * A missing rate key is zero.  A negative rate, a count other than nSpecies
+ * (nDims for neutralDrift), neutralMass <= 0 or a negative neutralVth is
+ * msg(ERROR).  mccAlloc returns NULL without a [collisions] section or when
+ * every rate is zero.  mccCollide runs one collision step on the settled
+ * velocities: between puMove and the next puAcc (msg(ERROR) while a fused
+ * puAcc's move is pending); the draws of step n of rank r are those of
+ * pinc_hip_collide_key(seed, n, r, s), n counted from 0 per Collisions.
+ * Where population:maxVel is finite the collided species' velocities are
+ * checked against it right away (the assert word pPosAssertInLocalFrame and
+ * the step read), so a neutral faster than the bound stops the run in the
+ * step that drew it.
+ * mccCounts: the elastic and charge-exchange collisions of species s since
+ * mccAlloc on this rank (waits for the stream). */
+typedef struct Collisions Collisions;
+Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo *mpiInfo);
+void mccCollide(Collisions *mcc, Population *pop);
+void mccFree(Collisions *mcc);
+void mccCounts(const Collisions *mcc, int s, unsigned long long out[2]);
 funPtr puExtractEmigrants3D_set(dictionary *ini);
 funPtr puExtractEmigrantsND_set(dictionary *ini);
 void puExtractEmigrants3D(Population *pop, MpiInfo *mpiInfo);
@@ -447,6 +483,12 @@ int pinc_sim_moments(PincSim *sim, int s, double *out);
  * to the global frame, nDims ints. */
 int pinc_sim_phase_hist(PincSim *sim, int s, const PhaseSpec *spec, double *hist, double *outside);
 int pinc_sim_offset(PincSim *sim, int *offset);
+/* Collisions (mccAlloc on the ini's [collisions]): every step collides right
+ * after puMove; pinc_sim_op(sim, "collide") runs one collision step on its
+ * own (non-zero, and a warning, without collisions).  pinc_sim_collisions:
+ * this rank's cumulative elastic and charge-exchange counts of species s
+ * (zeros without collisions; non-zero for a bad species). */
+int pinc_sim_collisions(PincSim *sim, int s, unsigned long long out[2]);
 int pinc_sim_emigrants(PincSim *sim, long *nEmigrants);
 int pinc_sim_species(PincSim *sim, double *charge, double *mass);
 int pinc_sim_sync(PincSim *sim);

@@ -372,6 +372,65 @@ int pinc_hip_accelerate_ngp(pinc_pop_t pop, int s, pinc_geom_t g, const double *
 int pinc_hip_deposit_tsc(pinc_pop_t pop, int s, pinc_geom_t g, double *rhoSlab, void *stream);
 int pinc_hip_accelerate_tsc(pinc_pop_t pop, int s, pinc_geom_t g, const double *Es, double *kePartial,
                             int *nBlocks, void *stream);
+/* Monte Carlo collisions of species s with a uniform neutral background (an
+ * extension: the reference has no collision module).  Null-free and direct:
+ * every live particle is tested in every launch, against a neutral drawn for
+ * it.  Process 0 is elastic (isotropic in the centre-of-mass frame), process 1
+ * charge exchange (the particle takes the neutral's velocity).  Ionisation,
+ * which would create particles, is not provided.  The rule is fixed, so that
+ * it can be restated (tests/collide_ref.py):
+ *   parameters   nu[k]    constant rate of process k per step
+ *                sig[k]   n_n sigma_k per unit of path
+ *                b = m_n / (m_s + m_n), a = 1 - b
+ *                vth, drift[d]   the neutrals' Maxwellian
+ *                h[d] = stepSize[d] / stepSize[0]
+ *   Code velocities v_d are cells of dimension d per step; the physics is done
+ *   on w_d = h_d v_d, and vth, drift and sig are in units of stepSize[0] and
+ *   the time step.
+ *   draws        key = pinc_hip_collide_key(seed, step, rank, s)
+ *                    = mix64(mix64(seed ^ mix64(step)) ^ mix64(rank PINC_MAX_SPECIES + s))
+ *                u_k = uni(key, 8 j + k), k = 0..7, for the particle at the
+ *                species-local index j = i - iStart[s] (mix64 and uni: the
+ *                counter RNG of pinc_hip_init_species).  Counter-based: a draw
+ *                that is not needed is not made, with the same result.
+ *   per particle, nd velocity components, in fp64:
+ *     1. R = sqrt(-2 ln u4), N_0 = R cos(2 pi u5), N_1 = R sin(2 pi u5),
+ *        N_2 = sqrt(-2 ln u6) cos(2 pi u7); n_d = drift_d + vth N_d, d < nd
+ *     2. g_d = w_d - n_d, g = sqrt(sum g_d^2)
+ *     3. r_k = nu_k + sig_k g, r = r_0 + r_1, P = -expm1(-r); the particle
+ *        collides iff u0 < P
+ *     4. elastic iff u1 r < r_0, else charge exchange
+ *     5. charge exchange: w' = n.  Elastic: w'_d = a w_d + b n_d + b g e_d
+ *        with the unit vector e
+ *          nd = 3: c = 1 - 2 u2, s = sqrt((1 - c)(1 + c)), phi = 2 pi u3,
+ *                  e = (s cos phi, s sin phi, c)
+ *          nd = 2: phi = 2 pi u2, e = (cos phi, sin phi)
+ *          nd = 1: e = +1 if u2 < 0.5, else -1
+ *     6. v'_d = w'_d / h_d
+ *   (cos and sin of 2 pi u are evaluated as cospi(2 u), sinpi(2 u); products
+ *   and sums are not fused.)
+ * A particle that does not collide is not written; positions are never read
+ * or written.  v[d] are the velocity arrays, as in pinc_hip_moments (indexed
+ * like pop.v[d], element 0 16-byte aligned).  counts[k] += the particles that
+ * underwent process k in this launch (device memory, accumulated, not
+ * cleared).  Errors (nothing is launched): s outside the population's species,
+ * nd outside 1..3, a null array or counter, a negative or non-finite rate or
+ * vth, a non-finite drift, b outside [0, 1], h_d <= 0. */
+typedef struct {
+	double nu[2];
+	double sig[2];
+	double b;
+	double vth;
+	double drift[3];
+	double h[3];
+	unsigned long long key;
+} pinc_collide_t;
+int pinc_hip_collide(pinc_pop_t pop, int s, double *const v[3], pinc_collide_t params, unsigned long long *counts,
+                     void *stream);
+/* the key of a launch (a pure host function: no device, no state) */
+unsigned long long pinc_hip_collide_key(unsigned long long seed, unsigned long long step, int rank, int s);
+/* particles per workgroup of pinc_hip_collide (a build constant; tests) */
+long pinc_hip_collide_chunk(void);
 /* pVelAssertMax (population.c:342-365) over species s: a velocity component
  * above maxVel sets bit 0 of *errFlag */
 int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *errFlag, void *stream);

@@ -3302,6 +3302,185 @@ __global__ __launch_bounds__(kThreads) void k_vel_assert(const double *__restric
 	if (bad) atomicOr(err, 1);
 }
 
+// ------------------------------------------------------- collisions -------
+// Monte Carlo collisions with a neutral background (an extension; the rule is
+// in include/pinc_hip.h).  A workgroup owns kColChunk consecutive slots from
+// the 16-byte aligned slot at or below iStart.  Only velocities are touched.
+// Draws are counters of the species-local index, so a particle's outcome does
+// not depend on which thread holds it.  Two instances per dimension count,
+// chosen by the launch's parameters:
+//  * EAGER (some sig != 0): the collision probability depends on the
+//    particle's speed relative to its neutral, so every particle's neutral is
+//    sampled.  The chunk frame of k_accel: velocities read as lane-contiguous
+//    16-B pairs;
+//  * otherwise the probability is the same for every particle and one draw
+//    decides, without the velocity.  Pass 1 makes that draw for every slot and
+//    lists the colliders' slots in LDS; pass 2 deals the list out densely, one
+//    collider per lane, and only there are velocities read and the neutral
+//    sampled.  (Deciding and colliding in one per-lane pass makes a wave run
+//    the whole collision branch whenever one of its 64 lanes collides: at 1 %
+//    colliding that is 1 - 0.99^64 = 0.47 of all wave iterations, and the
+//    launch took 1.62 ms of which 1.05 above a plain read, 0.47 of the eager
+//    form's 2.25.)
+// A collider's components are stored one by one (8 B per lane): nothing is
+// written for a particle that did not collide.  Measured against storing the
+// whole 16-B pair when either half collided, in a variant build of the
+// one-pass form (DESIGN.md section 4 "Collisions"; 128^3, 64 ppc): 1.62
+// against 1.63-1.64 ms with 1 % colliding, 2.82-2.85 either way in
+// cross-section mode, 3.28-3.34 against 3.19 ms with 63 % colliding: the pair
+// form wins only where most particles collide, which is not the regime the
+// operator is for.  The two counts are summed per wave (DPP), per block (LDS),
+// and added with one atomic per block and process that is not zero.
+constexpr int kColItems = 8;
+constexpr int kColChunk = kThreads * kColItems;
+
+// one particle: v[0..ND) in, and out if it collides; returns the process
+// (0 elastic, 1 charge exchange) or -1
+template <int ND>
+__device__ __forceinline__ int collide_one(const pinc_collide_t &c, unsigned long long base, double *v) {
+	const double u0 = uni(c.key, base);
+	double nn[ND], w[ND];
+	{
+		double sn, cs;
+		const double R = sqrt(-2.0 * log(uni(c.key, base + 4)));
+		sincospi(2.0 * uni(c.key, base + 5), &sn, &cs);
+		nn[0] = c.drift[0] + c.vth * (R * cs);
+		if constexpr (ND > 1) nn[1] = c.drift[1] + c.vth * (R * sn);
+		if constexpr (ND > 2)
+			nn[2] = c.drift[2] + c.vth * (sqrt(-2.0 * log(uni(c.key, base + 6))) * cospi(2.0 * uni(c.key, base + 7)));
+	}
+	double g2 = 0.0;
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+		w[d] = c.h[d] * v[d];
+		const double gd = w[d] - nn[d];
+		g2 += gd * gd;
+	}
+	const double g = sqrt(g2);
+	const double r0 = c.nu[0] + c.sig[0] * g, r1 = c.nu[1] + c.sig[1] * g, r = r0 + r1;
+	if (!(u0 < -expm1(-r))) return -1;
+	if (!(uni(c.key, base + 1) * r < r0)) {
+#pragma unroll
+		for (int d = 0; d < ND; d++) v[d] = nn[d] / c.h[d];
+		return 1;
+	}
+	double e[ND];
+	const double u2 = uni(c.key, base + 2);
+	if constexpr (ND == 3) {
+		double sn, cs;
+		const double ct = 1.0 - 2.0 * u2, st = sqrt((1.0 - ct) * (1.0 + ct));
+		sincospi(2.0 * uni(c.key, base + 3), &sn, &cs);
+		e[0] = st * cs;
+		e[1] = st * sn;
+		e[2] = ct;
+	} else if constexpr (ND == 2) {
+		sincospi(2.0 * u2, &e[1], &e[0]);
+	} else {
+		e[0] = u2 < 0.5 ? 1.0 : -1.0;
+	}
+	const double a = 1.0 - c.b, bg = c.b * g;
+#pragma unroll
+	for (int d = 0; d < ND; d++) v[d] = ((a * w[d] + c.b * nn[d]) + bg * e[d]) / c.h[d];
+	return 0;
+}
+
+template <int ND, bool EAGER>
+__global__ __launch_bounds__(kThreads) void k_collide(double *__restrict__ v0, double *__restrict__ v1,
+                                                      double *__restrict__ v2, long b0, long n, pinc_collide_t c,
+                                                      unsigned long long *__restrict__ counts) {
+	__shared__ int red[2 * kWaves];
+	// the parameters are read from LDS, into vector registers where they are
+	// used: held in scalar registers for the whole kernel, next to the
+	// constants of log, expm1 and sincospi, they spill scalar registers in 3-D
+	__shared__ pinc_collide_t par;
+	__shared__ int list[EAGER ? 1 : kColChunk];  // slots of the chunk's colliders
+	__shared__ int nList;
+	if (threadIdx.x == 0) {
+		par = c;
+		nList = 0;
+	}
+	__syncthreads();
+	double *vs[3] = {v0, v1, v2};
+	const long end = b0 + n;
+	const long chunk0 = (b0 & ~1L) + (long)blockIdx.x * kColChunk;
+	int nEl = 0, nCx = 0;
+	if constexpr (EAGER) {
+		const long cb = chunk0 + 2L * threadIdx.x;
+#pragma unroll
+		for (int k = 0; k < kColItems; k += 2) {
+			const long i = cb + 2L * kThreads * (k >> 1);
+			const bool ok[2] = {i >= b0 && i < end, i + 1 >= b0 && i + 1 < end};
+			if (!ok[0] && !ok[1]) continue;
+			double v[2][ND];
+#pragma unroll
+			for (int d = 0; d < ND; d++) {
+				if (ok[0] && ok[1]) {
+					const double2 t = *reinterpret_cast<const double2 *>(vs[d] + i);
+					v[0][d] = t.x;
+					v[1][d] = t.y;
+				} else {
+					v[0][d] = v[1][d] = vs[d][ok[0] ? i : i + 1];
+				}
+			}
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				if (!ok[h]) continue;
+				const int proc = collide_one<ND>(par, 8ull * (unsigned long long)(i + h - b0), v[h]);
+				if (proc < 0) continue;
+				nEl += proc == 0;
+				nCx += proc == 1;
+#pragma unroll
+				for (int d = 0; d < ND; d++) vs[d][i + h] = v[h][d];
+			}
+		}
+	} else {
+		// pass 1: r = nu_0 + nu_1 for every particle (sig_k g adds an exact
+		// zero), so P is the launch's, formed once with the rule's expression
+		const double P = -expm1(-(c.nu[0] + c.nu[1]));
+#pragma unroll
+		for (int k = 0; k < kColItems; k++) {
+			const int slot = k * kThreads + threadIdx.x;
+			const long i = chunk0 + slot;
+			if (i >= b0 && i < end && uni(c.key, 8ull * (unsigned long long)(i - b0)) < P) list[atomicAdd(&nList, 1)] = slot;
+		}
+		__syncthreads();
+		// pass 2: the colliders, one per lane (collide_one repeats the
+		// decision with the particle's own r: the same bits for a finite
+		// velocity, and no collision for one that is not)
+		// (unrolled: as a loop, the fp64 constants of log, expm1 and sincospi
+		// are hoisted out of it and held in 128 VGPRs and spilled SGPRs)
+		const int nl = nList;
+#pragma unroll
+		for (int q = 0; q < kColItems; q++) {
+			const int t = q * kThreads + threadIdx.x;
+			if (t >= nl) break;
+			const long i = chunk0 + list[t];
+			double v[ND];
+#pragma unroll
+			for (int d = 0; d < ND; d++) v[d] = vs[d][i];
+			const int proc = collide_one<ND>(par, 8ull * (unsigned long long)(i - b0), v);
+			if (proc < 0) continue;
+			nEl += proc == 0;
+			nCx += proc == 1;
+#pragma unroll
+			for (int d = 0; d < ND; d++) vs[d][i] = v[d];
+		}
+	}
+	// (every lane of every wave arrives here: the DPP sums need them all)
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+	for (int p = 0; p < 2; p++) {
+		const int t = wave_sum_i(p ? nCx : nEl);
+		if (lane == 0) red[p * kWaves + wv] = t;
+	}
+	__syncthreads();
+	if (threadIdx.x < 2) {
+		int t = 0;
+		for (int q = 0; q < kWaves; q++) t += red[threadIdx.x * kWaves + q];
+		if (t) atomicAdd(&counts[threadIdx.x], (unsigned long long)t);
+	}
+}
+
 }  // namespace
 
 // =========================================================== C ABI ========
@@ -3427,6 +3606,50 @@ extern "C" int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *er
 	hipLaunchKernelGGL(k_vel_assert, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, v.a, v.b, v.c, sp.b0, sp.n,
 	                   pop.nd, maxVel, errFlag);
 	return check_launch("velocity assert");
+}
+
+extern "C" long pinc_hip_collide_chunk(void) { return kColChunk; }
+
+// (mix64 of the device code, restated for the host: include/pinc_hip.h)
+extern "C" unsigned long long pinc_hip_collide_key(unsigned long long seed, unsigned long long step, int rank, int s) {
+	auto mix = [](unsigned long long z) {
+		z += 0x9E3779B97F4A7C15ULL;
+		z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+		z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+		return z ^ (z >> 31);
+	};
+	return mix(mix(seed ^ mix(step)) ^ mix((unsigned long long)((long)rank * PINC_MAX_SPECIES + s)));
+}
+
+extern "C" int pinc_hip_collide(pinc_pop_t pop, int s, double *const v[3], pinc_collide_t c, unsigned long long *counts,
+                                void *stream) {
+	if (s < 0 || s >= pop.nSpecies || pop.nd < 1 || pop.nd > 3 || !v || !counts)
+		return set_error(hipErrorInvalidValue, "collide: bad species, dimensions or null array");
+	for (int d = 0; d < pop.nd; d++) {
+		if (!v[d]) return set_error(hipErrorInvalidValue, "collide: null velocity array");
+		if (!(c.h[d] > 0.0) || !std::isfinite(c.h[d])) return set_error(hipErrorInvalidValue, "collide: h must be > 0");
+		if (!std::isfinite(c.drift[d])) return set_error(hipErrorInvalidValue, "collide: drift not finite");
+	}
+	for (int k = 0; k < 2; k++)
+		if (!(c.nu[k] >= 0.0) || !(c.sig[k] >= 0.0) || !std::isfinite(c.nu[k]) || !std::isfinite(c.sig[k]))
+			return set_error(hipErrorInvalidValue, "collide: a rate is negative or not finite");
+	if (!(c.b >= 0.0 && c.b <= 1.0)) return set_error(hipErrorInvalidValue, "collide: b outside [0, 1]");
+	if (!(c.vth >= 0.0) || !std::isfinite(c.vth)) return set_error(hipErrorInvalidValue, "collide: vth negative or not finite");
+	const Span sp = species_span(pop, s);
+	if (sp.n <= 0) return 0;
+	const long nb = chunk_blocks(sp.b0, sp.n, kColChunk);
+	hipStream_t st = (hipStream_t)stream;
+	const auto w = upto_nd(v, pop.nd);
+	// cross sections: every particle's neutral is sampled; rates alone: one
+	// draw decides and the colliders are processed densely (k_collide)
+	const bool eager = c.sig[0] != 0.0 || c.sig[1] != 0.0;
+	with_nd(pop.nd, [&](auto ND) {
+		if (eager)
+			hipLaunchKernelGGL((k_collide<ND, true>), dim3(nb), dim3(kThreads), 0, st, w.a, w.b, w.c, sp.b0, sp.n, c, counts);
+		else
+			hipLaunchKernelGGL((k_collide<ND, false>), dim3(nb), dim3(kThreads), 0, st, w.a, w.b, w.c, sp.b0, sp.n, c, counts);
+	});
+	return check_launch("collide");
 }
 
 extern "C" int pinc_hip_move_classify(pinc_pop_t pop, int s, int doMove, const double *thr,

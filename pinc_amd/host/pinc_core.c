@@ -13,6 +13,7 @@
 #include <ctype.h>
 #include <math.h>
 #include <stdarg.h>
+#include <strings.h>
 
 PincCtx g_pinc;
 
@@ -192,6 +193,26 @@ static const char *lookup(const dictionary *ini, const char *key) {
 }
 
 int iniHas(const dictionary *ini, const char *key) { return lookup(ini, key) != NULL; }
+
+/* the first key of [section] that is none of known[0..n) (names without the
+ * section, any case), or NULL; *count, if set, receives the section's keys */
+const char *pinc_ini_unknown_key(const dictionary *ini, const char *section, const char *const *known, int n, int *count) {
+	char pre[256];
+	snprintf(pre, sizeof(pre), "%s:", section);
+	lowercase(pre);
+	const size_t len = strlen(pre);
+	const char *bad = NULL;
+	int keys = 0;
+	for (int i = 0; i < ini->n; i++) {
+		if (strncmp(ini->e[i].key, pre, len)) continue;
+		keys++;
+		int ok = 0;
+		for (int k = 0; k < n && !ok; k++) ok = !strcasecmp(ini->e[i].key + len, known[k]);
+		if (!ok && !bad) bad = ini->e[i].key;
+	}
+	if (count) *count = keys;
+	return bad;
+}
 
 static const char *req(const dictionary *ini, const char *key) {
 	const char *v = lookup(ini, key);
@@ -389,6 +410,7 @@ static Units *unitsSI(const dictionary *ini) {
 }
 
 Units *uAlloc(dictionary *ini) {
+	pinc_mcc_mass_fraction(ini); /* (before the masses are rewritten below) */
 	/* parseIndirectInput (units.c:138-157) */
 	int nd = iniGetInt(ini, "grid:nDims");
 	int L[3];

@@ -364,6 +364,13 @@ void pinc_pending_vel(const Population *pop, int s, double *const *dst);
 const char *pinc_phase_spec_error(const PhaseSpec *spec, int nd);
 void pinc_literal_second_fold(const Population *pop, Grid *rho, int order);
 
+/* collisions:neutralMass's share of each pair mass, taken from the input's
+ * masses before uAlloc rewrites them (pinc_mcc.c) */
+void pinc_mcc_mass_fraction(dictionary *ini);
+/* the first key of [section] that is none of known[0..n) (names without the
+ * section), or NULL; *count, if set: the keys the section has (pinc_core.c) */
+const char *pinc_ini_unknown_key(const dictionary *ini, const char *section, const char *const *known, int n, int *count);
+
 /* helpers shared by the host translation units */
 void pinc_ctx_require(void);
 void pinc_check(int rc, const char *where);

@@ -1,0 +1,175 @@
+/*
+ * pinc_mcc.c -- Monte Carlo collisions with a neutral background (host side,
+ * C; an extension, the reference has no collision module).
+ *
+ *   mccAlloc     the ini's [collisions] section, validated
+ *   mccCollide   one pinc_hip_collide per species with a non-zero rate
+ *   mccCounts    cumulative elastic / charge-exchange counts
+ *
+ * The rule is pinc_hip_collide's (include/pinc_hip.h).
+ */
+#define _GNU_SOURCE
+#include "pinc_internal.h"
+#include <math.h>
+
+struct Collisions {
+	int nSpecies, nDims;
+	int active[PINC_MAX_SPECIES];        /* a rate of the species is not zero */
+	pinc_collide_t par[PINC_MAX_SPECIES]; /* key set per launch */
+	unsigned long long seed, step;
+	unsigned long long *counts;           /* device: [s][2] */
+};
+
+static const char *const kRateKeys[4] = {"collisions:elasticNu", "collisions:cexNu", "collisions:elasticSigma",
+                                         "collisions:cexSigma"};
+
+/* per-species values of a rate key (zeros if the key is missing) */
+static double *rate_arr(const dictionary *ini, const char *key, int ns) {
+	if (!iniHas(ini, key)) return calloc(ns, sizeof(double));
+	const int n = iniGetNElements(ini, key);
+	if (n != ns) msg(ERROR, "%s takes one value per species (%d), not %d", key, ns, n);
+	double *a = iniGetDoubleArr(ini, key, ns);
+	for (int s = 0; s < ns; s++)
+		if (!(a[s] >= 0.0) || !isfinite(a[s])) msg(ERROR, "%s must be >= 0 and finite (species %d: %g)", key, s, a[s]);
+	return a;
+}
+
+/* uAlloc rewrites population:mass (SI, then computational particles of
+ * normalised mass): the neutral's share of the pair mass b = m_n / (m_s + m_n)
+ * is taken from the input's own values before that (pinc_core.c calls this at
+ * the top of uAlloc) and kept in the ini for mccAlloc */
+void pinc_mcc_mass_fraction(dictionary *ini) {
+	/* the derived key is this library's own: an input that sets it would
+	 * override the masses without a word */
+	if (iniHas(ini, "collisions:neutralMassFraction"))
+		msg(ERROR, "collisions:neutralMassFraction is derived from collisions:neutralMass and population:mass; "
+		           "it cannot be set in the input");
+	if (!iniHas(ini, "collisions:neutralMass")) return;
+	const int ns = iniGetInt(ini, "population:nSpecies");
+	const double mn = iniGetDouble(ini, "collisions:neutralMass");
+	if (!(mn > 0.0) || !isfinite(mn)) msg(ERROR, "collisions:neutralMass must be > 0 and finite, not %g", mn);
+	double *m = iniGetDoubleArr(ini, "population:mass", ns);
+	double b[PINC_MAX_SPECIES] = {0};
+	for (int s = 0; s < ns && s < PINC_MAX_SPECIES; s++) b[s] = mn / (m[s] + mn);
+	iniSetDoubleArr(ini, "collisions:neutralMassFraction", b, ns < PINC_MAX_SPECIES ? ns : PINC_MAX_SPECIES);
+	free(m);
+}
+
+Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo *mpiInfo) {
+	(void)mpiInfo;
+	const int ns = pop->nSpecies, nd = pop->nDims;
+	static const char *const known[9] = {"elasticNu", "cexNu", "elasticSigma", "cexSigma", "neutralMass", "neutralVth",
+	                                     "neutralDrift", "seed", "neutralMassFraction"};
+	int present = 0;
+	const char *unknown = pinc_ini_unknown_key(ini, "collisions", known, 9, &present);
+	if (!present) return NULL;
+	if (unknown)
+		msg(ERROR, "%s is no key of [collisions] (elasticNu, cexNu, elasticSigma, cexSigma, neutralMass, neutralVth, "
+		           "neutralDrift, seed)", unknown);
+	if (ns > PINC_MAX_SPECIES) msg(ERROR, "collisions: more than %d species", PINC_MAX_SPECIES);
+
+	double *rate[4];
+	for (int k = 0; k < 4; k++) rate[k] = rate_arr(ini, kRateKeys[k], ns);
+	double vth = iniHas(ini, "collisions:neutralVth") ? iniGetDouble(ini, "collisions:neutralVth") : 0.0;
+	if (!(vth >= 0.0) || !isfinite(vth)) msg(ERROR, "collisions:neutralVth must be >= 0 and finite, not %g", vth);
+	double drift[3] = {0, 0, 0};
+	if (iniHas(ini, "collisions:neutralDrift")) {
+		const int n = iniGetNElements(ini, "collisions:neutralDrift");
+		if (n != nd) msg(ERROR, "collisions:neutralDrift takes one value per dimension (%d), not %d", nd, n);
+		double *a = iniGetDoubleArr(ini, "collisions:neutralDrift", nd);
+		for (int d = 0; d < nd; d++) {
+			if (!isfinite(a[d])) msg(ERROR, "collisions:neutralDrift must be finite");
+			drift[d] = a[d];
+		}
+		free(a);
+	}
+	int anyElastic = 0, any = 0;
+	for (int s = 0; s < ns; s++) {
+		anyElastic |= rate[0][s] > 0 || rate[2][s] > 0;
+		any |= rate[0][s] > 0 || rate[1][s] > 0 || rate[2][s] > 0 || rate[3][s] > 0;
+	}
+	double b[PINC_MAX_SPECIES] = {0};
+	if (iniHas(ini, "collisions:neutralMass")) {
+		const double mn = iniGetDouble(ini, "collisions:neutralMass");
+		if (!(mn > 0.0) || !isfinite(mn)) msg(ERROR, "collisions:neutralMass must be > 0 and finite, not %g", mn);
+		if (iniHas(ini, "collisions:neutralMassFraction")) {
+			double *f = iniGetDoubleArr(ini, "collisions:neutralMassFraction", ns);
+			for (int s = 0; s < ns; s++) b[s] = f[s];
+			free(f);
+		} else {
+			/* an ini that uAlloc has not rewritten: the masses as they stand */
+			double *m = iniGetDoubleArr(ini, "population:mass", ns);
+			for (int s = 0; s < ns; s++) b[s] = mn / (m[s] + mn);
+			free(m);
+		}
+	} else if (anyElastic) {
+		msg(ERROR, "collisions:neutralMass is required with an elastic rate");
+	}
+	Collisions *C = NULL;
+	if (any) {
+		double *step = iniGetDoubleArr(ini, "grid:stepSize", nd);
+		C = calloc(1, sizeof(*C));
+		C->nSpecies = ns;
+		C->nDims = nd;
+		C->seed = iniHas(ini, "collisions:seed") ? (unsigned long long)iniGetLongInt(ini, "collisions:seed") : 0ULL;
+		for (int s = 0; s < ns; s++) {
+			pinc_collide_t *p = &C->par[s];
+			p->nu[0] = rate[0][s];
+			p->nu[1] = rate[1][s];
+			p->sig[0] = rate[2][s];
+			p->sig[1] = rate[3][s];
+			p->b = b[s];
+			p->vth = vth;
+			for (int d = 0; d < 3; d++) {
+				p->drift[d] = drift[d];
+				p->h[d] = d < nd ? step[d] / step[0] : 1.0;
+			}
+			C->active[s] = p->nu[0] > 0 || p->nu[1] > 0 || p->sig[0] > 0 || p->sig[1] > 0;
+		}
+		free(step);
+		pinc_ctx_require();
+		pinc_check(pinc_hip_malloc((void **)&C->counts, 2 * PINC_MAX_SPECIES * sizeof(unsigned long long)),
+		           "collision counters");
+		pinc_check(pinc_hip_memset(C->counts, 0, 2 * PINC_MAX_SPECIES * sizeof(unsigned long long), g_pinc.stream),
+		           "collision counters");
+	}
+	for (int k = 0; k < 4; k++) free(rate[k]);
+	return C;
+}
+
+void mccCollide(Collisions *C, Population *pop) {
+	if (!C) return;
+	pinc_pop_flush_host(pop);
+	PincDevPop *dv = pop->dev;
+	if (dv->pending)
+		msg(ERROR, "mccCollide with a fused puAcc's move pending: collide the settled velocities, after puMove");
+	pinc_pop_t p = pinc_devpop(pop);
+	for (int s = 0; s < C->nSpecies; s++) {
+		if (!C->active[s]) continue;
+		pinc_collide_t par = C->par[s];
+		par.key = pinc_hip_collide_key(C->seed, C->step, g_pinc.rank, s);
+		pinc_check(pinc_hip_collide(p, s, p.v, par, C->counts + 2 * s, g_pinc.stream), "collide");
+		/* a collider's new velocity (a fast neutral's, in charge exchange) is
+		 * held to population:maxVel now, not at the next kick: the assert
+		 * word is read by the step's pPosAssertInLocalFrame */
+		if (isfinite(g_pinc.maxVel)) {
+			pinc_check(pinc_hip_vel_assert(p, s, g_pinc.maxVel, g_pinc.dErr, g_pinc.stream), "collide: maxVel");
+			g_pinc.errSerial++;
+		}
+	}
+	C->step++;
+	/* (pinc_pop_flush_host left the device arrays the truth: pSyncToHost reads them) */
+}
+
+void mccCounts(const Collisions *C, int s, unsigned long long out[2]) {
+	out[0] = out[1] = 0;
+	if (!C) return;
+	if (s < 0 || s >= C->nSpecies) msg(ERROR, "mccCounts: species %d out of range", s);
+	pinc_check(pinc_hip_d2h(out, C->counts + 2 * s, 2 * sizeof(unsigned long long), g_pinc.stream), "collision counters");
+}
+
+void mccFree(Collisions *C) {
+	if (!C) return;
+	pinc_hip_free(C->counts);
+	free(C);
+}

@@ -6,7 +6,7 @@
  * Loop order per step (main.c:197-274, single-add harness of SURVEY.md
  * Appendix A; literal=1 adds main.c:231-235's second FROMHALO add and the
  * extra solve):
- *   puMove -> extractEmigrants -> puMigrate -> distr -> gHaloOp(add,rho,FROM)
+ *   puMove [-> mccCollide] -> extractEmigrants -> puMigrate -> distr -> gHaloOp(add,rho,FROM)
  *   -> solve -> gHaloOp(set,phi,TO) -> gFinDiff1st -> gHaloOp(set,E,TO)
  *   -> gMul(E,-1) -> acc (+KE) -> pSumKinEnergy -> gPotEnergy
  * The per-step asserts pVelAssertMax / pPosAssertInLocalFrame are folded into
@@ -68,6 +68,7 @@ struct PincSim {
 	double phaseOutside;
 	long long phaseFile[PINC_MAX_SPECIES];
 	int phaseOutput;   /* their files are open */
+	Collisions *mcc;   /* the ini's [collisions] (mccAlloc), or NULL */
 };
 
 static int g_simActive = 0;
@@ -259,6 +260,7 @@ static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
 	if (S->momEvery < 0) msg(ERROR, "diagnostics:moments must be >= 0");
 	if (S->momEvery > 0) mom_alloc(S);
 	phase_read_ini(S);
+	S->mcc = mccAlloc(ini, S->pop, S->mpi);
 	return S;
 }
 
@@ -309,6 +311,9 @@ static void sim_fields(PincSim *S) {
 static void sim_step(PincSim *S) {
 	Population *pop = S->pop;
 	puMove(pop, NULL);
+	/* collisions act on the settled velocities, before the extraction: an
+	 * emigrant carries its new velocity with it */
+	if (S->mcc) mccCollide(S->mcc, pop);
 	S->extractEmigrants(pop, S->mpi);
 	puMigrate(pop, S->mpi, S->rho);
 	/* pPosAssertInLocalFrame (main.c:219) before anything deposits an
@@ -398,6 +403,7 @@ static void sim_free(PincSim *S) {
 	output_close(S);
 	mom_free(S);
 	phase_free(S);
+	mccFree(S->mcc);
 	pinc_obj_free(S->obj);
 	if (S->solverFree) S->solverFree(S->solver);
 	gFree(S->E);
@@ -511,6 +517,12 @@ int pinc_sim_op(PincSim *S, const char *op) {
 			return 1;
 		}
 		for (int s = 0; s < S->pop->nSpecies; s++) phase_compute(S, s);
+	} else if (!strcmp(op, "collide")) {
+		if (!S->mcc) {
+			msg(WARNING, "op collide without [collisions] (or with every rate zero)");
+			return 1;
+		}
+		mccCollide(S->mcc, S->pop);
 	} else if (!strcmp(op, "step")) sim_step(S);
 	else {
 		msg(WARNING, "unknown op %s", op);
@@ -667,6 +679,16 @@ int pinc_sim_phase_hist(PincSim *S, int s, const PhaseSpec *spec, double *hist, 
 		return 1;
 	}
 	puPhaseHist(S->pop, s, spec, S->mpi, hist, outside);
+	return 0;
+}
+
+int pinc_sim_collisions(PincSim *S, int s, unsigned long long out[2]) {
+	out[0] = out[1] = 0;
+	if (s < 0 || s >= S->pop->nSpecies) {
+		msg(WARNING, "pinc_sim_collisions: species %d out of range", s);
+		return 1;
+	}
+	mccCounts(S->mcc, s, out);
 	return 0;
 }
 

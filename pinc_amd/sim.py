@@ -211,6 +211,16 @@ class Sim:
             raise ValueError(f"phase_space: bad species {s} or spec (axes {axes}, bins {bins}, lo {lo}, hi {hi})")
         return out, outside.value
 
+    def collisions(self, s: int) -> tuple[int, int]:
+        """(elastic, charge exchange): this rank's collisions of species s
+        with the neutral background since the simulation was created (the
+        ini's [collisions] section; zeros without one).  op("collide") runs
+        one collision step on its own."""
+        out = (C.c_ulonglong * 2)()
+        if HOST.pinc_sim_collisions(self._h, s, out):
+            raise ValueError(f"collisions: no species {s}")
+        return int(out[0]), int(out[1])
+
     @property
     def offset(self) -> np.ndarray:
         """This rank's offset of the local frame (particles()) to the global
