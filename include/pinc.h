@@ -281,6 +281,15 @@ void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *m
  *   neutralVth              thermal speed per component (default 0)
  *   neutralDrift            nDims values (default 0)
  *   seed                    of the draws (default 0)
+ *   ionNu, ionSigma         electron-impact ionisation by species s: rate per
+ *                           step and n_n sigma per unit of path, one value per
+ *                           species
+ *   ionThreshold            the threshold speed of each species, relative to
+ *                           the neutral, in stepSize[0] per step (default 0)
+ *   ionSpecies              per species, the species that receives its ions:
+ *                           required with an ionisation rate, read for the
+ *                           species that have one, a valid index other than
+ *                           the projectile's (else msg(ERROR))
  * uAlloc takes the neutral's share of each pair mass, b = m_n / (m_s + m_n),
  * from the input's masses before it rewrites them and keeps it in the
  * dictionary as collisions:neutralMassFraction, which mccAlloc reads (on a
@@ -299,12 +308,24 @@ void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *m
  * the step read), so a neutral faster than the bound stops the run in the
  * step that drew it.
  * mccCounts: the elastic and charge-exchange collisions of species s since
- * mccAlloc on this rank (waits for the stream). */
+ * mccAlloc on this rank (waits for the stream).
+ * mccIonize runs one ionisation step (the rule at pinc_hip_ionize): after
+ * puMigrate, where every particle is inside the local frame, and before the
+ * deposit, which then carries the new pair's charge (msg(ERROR) while a fused
+ * puAcc's move is pending).  Each projectile species' births join the tail of
+ * the projectile and of its ionSpecies as immigrants do; births that do not
+ * fit either species' allocation are msg(ERROR).  Its draws are those of
+ * pinc_hip_ionize_key(seed, n, r, s) with a call counter n of its own, so
+ * mccCollide's draws are the same with and without ionisation.  Nothing is
+ * launched without an ionisation rate.  mccIonizations: the births caused by
+ * projectile species s since mccAlloc on this rank. */
 typedef struct Collisions Collisions;
 Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo *mpiInfo);
 void mccCollide(Collisions *mcc, Population *pop);
 void mccFree(Collisions *mcc);
 void mccCounts(const Collisions *mcc, int s, unsigned long long out[2]);
+void mccIonize(Collisions *mcc, Population *pop);
+unsigned long long mccIonizations(const Collisions *mcc, int s);
 funPtr puExtractEmigrants3D_set(dictionary *ini);
 funPtr puExtractEmigrantsND_set(dictionary *ini);
 void puExtractEmigrants3D(Population *pop, MpiInfo *mpiInfo);
@@ -487,8 +508,12 @@ int pinc_sim_offset(PincSim *sim, int *offset);
  * after puMove; pinc_sim_op(sim, "collide") runs one collision step on its
  * own (non-zero, and a warning, without collisions).  pinc_sim_collisions:
  * this rank's cumulative elastic and charge-exchange counts of species s
- * (zeros without collisions; non-zero for a bad species). */
+ * (zeros without collisions; non-zero for a bad species).  Ionisation
+ * (collisions:ionNu, ionSigma): every step, and the init sequence, ionises
+ * right after puMigrate; pinc_sim_op(sim, "ionize") runs one ionisation step on
+ * its own.  pinc_sim_ionizations: mccIonizations of species s into *births. */
 int pinc_sim_collisions(PincSim *sim, int s, unsigned long long out[2]);
+int pinc_sim_ionizations(PincSim *sim, int s, unsigned long long *births);
 int pinc_sim_emigrants(PincSim *sim, long *nEmigrants);
 int pinc_sim_species(PincSim *sim, double *charge, double *mass);
 int pinc_sim_sync(PincSim *sim);

@@ -377,8 +377,8 @@ int pinc_hip_accelerate_tsc(pinc_pop_t pop, int s, pinc_geom_t g, const double *
  * every live particle is tested in every launch, against a neutral drawn for
  * it.  Process 0 is elastic (isotropic in the centre-of-mass frame), process 1
  * charge exchange (the particle takes the neutral's velocity).  Ionisation,
- * which would create particles, is not provided.  The rule is fixed, so that
- * it can be restated (tests/collide_ref.py):
+ * which creates particles, is pinc_hip_ionize's, below.  The rule is fixed, so
+ * that it can be restated (tests/collide_ref.py):
  *   parameters   nu[k]    constant rate of process k per step
  *                sig[k]   n_n sigma_k per unit of path
  *                b = m_n / (m_s + m_n), a = 1 - b
@@ -431,6 +431,70 @@ int pinc_hip_collide(pinc_pop_t pop, int s, double *const v[3], pinc_collide_t p
 unsigned long long pinc_hip_collide_key(unsigned long long seed, unsigned long long step, int rank, int s);
 /* particles per workgroup of pinc_hip_collide (a build constant; tests) */
 long pinc_hip_collide_chunk(void);
+/* Electron-impact ionisation of the same neutral background by species s (an
+ * extension): a projectile faster than a threshold, relative to a neutral
+ * drawn for it, loses the threshold energy, and an electron of species s and
+ * an ion of species `target` are born where it stands.  The neutral is taken
+ * as infinitely heavy, and what is left of the relative energy is shared by
+ * the two electrons.  Every live particle is tested in every launch.  The rule
+ * is fixed, so that it can be restated (tests/ionize_ref.py):
+ *   parameters   nu       constant ionisation rate per step
+ *                sig      n_n sigma per unit of path
+ *                wth      threshold speed
+ *                vth, drift[d], h[d]   as pinc_collide_t
+ *                target   the species that receives the ions, != s
+ *   Units as at pinc_hip_collide: the physics is done on w_d = h_d v_d; wth,
+ *   vth, drift and sig are in units of stepSize[0] and the time step.
+ *   draws        key = pinc_hip_ionize_key(seed, step, rank, s)
+ *                    = mix64(pinc_hip_collide_key(seed, step, rank, s) ^ 0x696F6E697365)
+ *                u_k = uni(key, 16 j + k), k = 0..15, for the particle at the
+ *                species-local index j = i - iStart[s] (mix64, uni: as
+ *                pinc_hip_collide).  Counter-based: a draw that is not needed
+ *                is not made, with the same result.
+ *   per live particle, nd components, in fp64, for d ascending:
+ *     1. the neutral n_d exactly as in step 1 of pinc_hip_collide, from u4..u7
+ *        of this stream
+ *     2. w_d = h_d v_d, g_d = w_d - n_d, G = sum g_d^2, g = sqrt(G)
+ *     3. r = nu + sig g, P = -expm1(-r), W = wth wth; the particle ionises
+ *        iff G > W && u0 < P
+ *     4. rem = G - W, f = u1, g1 = sqrt(f rem), g2 = sqrt((1 - f) rem)
+ *     5. unit vectors by step 5 of pinc_hip_collide for this nd: e1 from
+ *        (u2, u3), e2 from (u8, u9)
+ *     6. the parent gets v'_d = (n_d + g1 e1_d) / h_d; the new electron
+ *        (n_d + g2 e2_d) / h_d and the new ion n_d / h_d, both at the parent's
+ *        position, copied bit for bit.  In the neutral's frame
+ *        |w' - n|^2 + |w_new - n|^2 = G - W.
+ *   (cospi, sinpi as at pinc_hip_collide; products and sums are not fused.)
+ * Placement: the births of a launch are numbered k = 0, 1, ... in ascending
+ * parent index; birth k writes the electron to slot iStop[s] + k and the ion to
+ * slot iStop[target] + k.  Only [iStart[s], iStop[s]) as passed in is tested.
+ * The ranges are the host's: the kernel does not change them, and the caller
+ * adds the births (res[0]'s increase) to both iStop.  res is device memory:
+ * res[0] += the births of this launch.  If they exceed the free slots of either
+ * species (iStart[q + 1] - iStop[q]), nothing is written: no parent, no child,
+ * not res[0]; res[1] is set to 1 and the call still returns 0.  A particle that
+ * does not ionise is not written; positions of existing particles are never
+ * written.  work: pinc_hip_ionize_work(n) ints of device scratch for n live
+ * particles (workInts of them are there).  Errors (nothing is launched): s or
+ * target outside the population's species, or equal; nd outside 1..3; a null
+ * array; a live range outside its species' slots; work too small; a negative
+ * or non-finite nu, sig, wth or vth; a non-finite drift; h_d <= 0. */
+typedef struct {
+	double nu;        /* constant ionisation rate per step */
+	double sig;       /* n_n sigma per unit of path */
+	double wth;       /* threshold speed, in stepSize[0] per step */
+	double vth, drift[3], h[3];   /* as pinc_collide_t */
+	int target;       /* species that receives the ions, != s */
+	unsigned long long key;
+} pinc_ionize_t;
+int pinc_hip_ionize(pinc_pop_t pop, int s, pinc_ionize_t par, int *work, long workInts, unsigned long long *res,
+                    void *stream);
+/* ints of scratch for n live particles */
+long pinc_hip_ionize_work(long n);
+/* particles per workgroup of pinc_hip_ionize (a build constant; tests) */
+long pinc_hip_ionize_chunk(void);
+/* the key of a launch (a pure host function: no device, no state) */
+unsigned long long pinc_hip_ionize_key(unsigned long long seed, unsigned long long step, int rank, int s);
 /* pVelAssertMax (population.c:342-365) over species s: a velocity component
  * above maxVel sets bit 0 of *errFlag */
 int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *errFlag, void *stream);

@@ -3481,6 +3481,211 @@ __global__ __launch_bounds__(kThreads) void k_collide(double *__restrict__ v0, d
 	}
 }
 
+// ------------------------------------------------------- ionisation -------
+// Electron-impact ionisation against the same neutral background (an
+// extension; the rule is in include/pinc_hip.h).  The one process that creates
+// particles: birth k of a launch, counted in ascending parent index, puts an
+// electron at slot iStop[s] + k and an ion at iStop[target] + k.  That order
+// needs every block's first k before anything is written, so the kernel runs
+// twice around a scan of the blocks' counts (pinc_hip_ionize):
+//  * WRITE = false decides every particle and writes the block's births;
+//  * WRITE = true tests the total against the free slots of both species (a
+//    launch that does not fit writes nothing but res[1]), decides again -- the
+//    draws are counters, the arithmetic is the same code: the same bits --
+//    and ranks the births of an item by a wave ballot and the waves' counts
+//    in LDS, the items in turn.
+// A workgroup owns kIonChunk consecutive slots in k_collide's frame; item q of
+// thread t is slot q kThreads + t, so that items, waves and lanes ascend with
+// the index.  Two instances of each, chosen as k_collide's:
+//  * EAGER (sig != 0): the probability depends on the particle's speed, so
+//    every live slot is an entry of the second stage;
+//  * otherwise u0 < P, with the launch's one P, is necessary: the first stage
+//    makes that draw alone and lists the candidates in LDS in index order
+//    (the same ballot ranking), and the second stage deals them out densely,
+//    so that the neutral's logarithms and the threshold test run on full
+//    waves (the reason is k_collide's, measured there).
+// The second stage is unrolled and the parameters come from LDS for the
+// register reasons given at k_collide.
+constexpr int kIonItems = 8;
+constexpr int kIonChunk = kThreads * kIonItems;
+
+// the ranges of one launch: live particles [b0, b0 + n) of the projectile, the
+// first free slot of the projectile and of the target and their free slots
+struct IonSpan {
+	long b0, n, dstS, dstT, freeS, freeT;
+};
+
+// step 5's unit vector from the draws at counters cb and cb + 1
+template <int ND>
+__device__ __forceinline__ void ion_unit(unsigned long long key, unsigned long long cb, double *e) {
+	const double ua = uni(key, cb);
+	if constexpr (ND == 3) {
+		double sn, cs;
+		const double ct = 1.0 - 2.0 * ua, st = sqrt((1.0 - ct) * (1.0 + ct));
+		sincospi(2.0 * uni(key, cb + 1), &sn, &cs);
+		e[0] = st * cs;
+		e[1] = st * sn;
+		e[2] = ct;
+	} else if constexpr (ND == 2) {
+		sincospi(2.0 * ua, &e[1], &e[0]);
+	} else {
+		e[0] = ua < 0.5 ? 1.0 : -1.0;
+	}
+}
+
+// steps 1 to 3 for one particle of velocity v: its neutral nn and, if it
+// ionises, rem = G - W
+template <int ND>
+__device__ __forceinline__ bool ion_decide(const pinc_ionize_t &c, unsigned long long base, const double *v, double *nn,
+                                           double &rem) {
+	const double u0 = uni(c.key, base);
+	{
+		double sn, cs;
+		const double R = sqrt(-2.0 * log(uni(c.key, base + 4)));
+		sincospi(2.0 * uni(c.key, base + 5), &sn, &cs);
+		nn[0] = c.drift[0] + c.vth * (R * cs);
+		if constexpr (ND > 1) nn[1] = c.drift[1] + c.vth * (R * sn);
+		if constexpr (ND > 2)
+			nn[2] = c.drift[2] + c.vth * (sqrt(-2.0 * log(uni(c.key, base + 6))) * cospi(2.0 * uni(c.key, base + 7)));
+	}
+	double G = 0.0;
+#pragma unroll
+	for (int d = 0; d < ND; d++) {
+		const double gd = c.h[d] * v[d] - nn[d];
+		G += gd * gd;
+	}
+	const double r = c.nu + c.sig * sqrt(G), W = c.wth * c.wth;
+	if (!(G > W && u0 < -expm1(-r))) return false;
+	rem = G - W;
+	return true;
+}
+
+template <int ND, bool EAGER, bool WRITE>
+__global__ __launch_bounds__(kThreads) void k_ionize(double *__restrict__ x0, double *__restrict__ x1,
+                                                     double *__restrict__ x2, double *__restrict__ v0,
+                                                     double *__restrict__ v1, double *__restrict__ v2, IonSpan sp,
+                                                     pinc_ionize_t c, int *__restrict__ counts,
+                                                     const int *__restrict__ offsets, int nb,
+                                                     unsigned long long *__restrict__ res) {
+	__shared__ pinc_ionize_t par;
+	__shared__ int list[EAGER ? 1 : kIonChunk];  // slots of the chunk's candidates, ascending
+	__shared__ int cnt[kIonItems * kWaves];      // candidates per item and wave
+	__shared__ int wcnt[2][kWaves];              // births per wave of an item (even and odd items)
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	int run = 0;  // births before the current item: of the launch (WRITE), of this thread (otherwise)
+	if constexpr (WRITE) {
+		// (the same for every block: all of them leave, or none)
+		const long total = offsets[nb];
+		if (total > sp.freeS || total > sp.freeT) {
+			if (blockIdx.x == 0 && threadIdx.x == 0) res[1] = 1;
+			return;
+		}
+		if (blockIdx.x == 0 && threadIdx.x == 0 && total) atomicAdd(&res[0], (unsigned long long)total);
+		run = offsets[blockIdx.x];
+	}
+	if (threadIdx.x == 0) par = c;
+	__syncthreads();
+	double *xs[3] = {x0, x1, x2}, *vs[3] = {v0, v1, v2};
+	const long end = sp.b0 + sp.n;
+	const long chunk0 = (sp.b0 & ~1L) + (long)blockIdx.x * kIonChunk;
+	int nl = kIonChunk;  // entries of the second stage
+	if constexpr (!EAGER) {
+		// r = nu for every particle (sig g adds an exact zero), so P is the
+		// launch's, formed once with the rule's expression
+		const double P = -expm1(-c.nu);
+		unsigned mask = 0;
+#pragma unroll
+		for (int k = 0; k < kIonItems; k++) {
+			const long i = chunk0 + k * kThreads + threadIdx.x;
+			const bool cand = i >= sp.b0 && i < end && uni(c.key, 16ull * (unsigned long long)(i - sp.b0)) < P;
+			const unsigned long long bal = __ballot(cand);
+			if (lane == 0) cnt[k * kWaves + wv] = __popcll(bal);
+			mask |= (unsigned)cand << k;
+		}
+		__syncthreads();
+		nl = 0;
+#pragma unroll
+		for (int k = 0; k < kIonItems; k++) {
+			const bool cand = (mask >> k) & 1;
+			const unsigned long long bal = __ballot(cand);
+			int before = 0, tot = 0;
+#pragma unroll
+			for (int q = 0; q < kWaves; q++) {
+				before += q < wv ? cnt[k * kWaves + q] : 0;
+				tot += cnt[k * kWaves + q];
+			}
+			if (cand) list[nl + before + __popcll(bal & lanemask_lt())] = k * kThreads + threadIdx.x;
+			nl += tot;
+		}
+		__syncthreads();
+	}
+	// second stage: one entry per lane (ion_decide repeats a candidate's
+	// decision with the particle's own r: the same bits for a finite velocity,
+	// and no birth for one that is not)
+#pragma unroll
+	for (int q = 0; q < kIonItems; q++) {
+		if (q * kThreads >= nl) break;  // (the same for the whole block)
+		const int t = q * kThreads + threadIdx.x;
+		long i = -1;
+		if constexpr (EAGER) {
+			if (chunk0 + t >= sp.b0 && chunk0 + t < end) i = chunk0 + t;
+		} else {
+			if (t < nl) i = chunk0 + list[t];
+		}
+		bool hit = false;
+		double nn[ND], rem = 0.0;
+		if (i >= 0) {
+			double v[ND];
+#pragma unroll
+			for (int d = 0; d < ND; d++) v[d] = vs[d][i];
+			hit = ion_decide<ND>(par, 16ull * (unsigned long long)(i - sp.b0), v, nn, rem);
+		}
+		if constexpr (!WRITE) {
+			run += hit;
+		} else {
+			const unsigned long long bal = __ballot(hit);
+			if (lane == 0) wcnt[q & 1][wv] = __popcll(bal);
+			__syncthreads();
+			int before = 0, tot = 0;
+#pragma unroll
+			for (int w = 0; w < kWaves; w++) {
+				before += w < wv ? wcnt[q & 1][w] : 0;
+				tot += wcnt[q & 1][w];
+			}
+			if (hit) {
+				const long k = (long)run + before + __popcll(bal & lanemask_lt());
+				const unsigned long long base = 16ull * (unsigned long long)(i - sp.b0);
+				const double f = uni(par.key, base + 1);
+				const double g1 = sqrt(f * rem), g2 = sqrt((1.0 - f) * rem);
+				double e1[ND], e2[ND];
+				ion_unit<ND>(par.key, base + 2, e1);
+				ion_unit<ND>(par.key, base + 8, e2);
+#pragma unroll
+				for (int d = 0; d < ND; d++) {
+					const double x = xs[d][i];
+					vs[d][i] = (nn[d] + g1 * e1[d]) / par.h[d];
+					xs[d][sp.dstS + k] = x;
+					vs[d][sp.dstS + k] = (nn[d] + g2 * e2[d]) / par.h[d];
+					xs[d][sp.dstT + k] = x;
+					vs[d][sp.dstT + k] = nn[d] / par.h[d];
+				}
+			}
+			run += tot;
+		}
+	}
+	if constexpr (!WRITE) {
+		// (every lane of every wave arrives here: the DPP sum needs them all)
+		const int t = wave_sum_i(run);
+		if (lane == 0) wcnt[0][wv] = t;
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			int s = 0;
+			for (int w = 0; w < kWaves; w++) s += wcnt[0][w];
+			counts[blockIdx.x] = s;
+		}
+	}
+}
+
 }  // namespace
 
 // =========================================================== C ABI ========
@@ -3650,6 +3855,70 @@ extern "C" int pinc_hip_collide(pinc_pop_t pop, int s, double *const v[3], pinc_
 			hipLaunchKernelGGL((k_collide<ND, false>), dim3(nb), dim3(kThreads), 0, st, w.a, w.b, w.c, sp.b0, sp.n, c, counts);
 	});
 	return check_launch("collide");
+}
+
+extern "C" long pinc_hip_ionize_chunk(void) { return kIonChunk; }
+
+// the blocks' counts [nb] | their offsets [nb + 1] | scan_ints' work, for the
+// nb blocks of n particles at an odd start (chunk_blocks)
+extern "C" long pinc_hip_ionize_work(long n) {
+	const long nb = ceil_div((n > 0 ? n : 0) + 1, (long)kIonChunk);
+	return nb + (nb + 1) + 2 * ceil_div(nb, (long)kScanBlock) + 1;
+}
+
+extern "C" unsigned long long pinc_hip_ionize_key(unsigned long long seed, unsigned long long step, int rank, int s) {
+	unsigned long long z = pinc_hip_collide_key(seed, step, rank, s) ^ 0x696F6E697365ULL;
+	// (mix64, as in pinc_hip_collide_key)
+	z += 0x9E3779B97F4A7C15ULL;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+	return z ^ (z >> 31);
+}
+
+extern "C" int pinc_hip_ionize(pinc_pop_t pop, int s, pinc_ionize_t c, int *work, long workInts, unsigned long long *res,
+                               void *stream) {
+	const int t = c.target;
+	if (s < 0 || s >= pop.nSpecies || t < 0 || t >= pop.nSpecies || s == t || pop.nSpecies > PINC_MAX_SPECIES)
+		return set_error(hipErrorInvalidValue, "ionize: bad projectile or target species");
+	if (pop.nd < 1 || pop.nd > 3 || !work || !res)
+		return set_error(hipErrorInvalidValue, "ionize: bad dimensions or null array");
+	for (int d = 0; d < pop.nd; d++) {
+		if (!pop.x[d] || !pop.v[d]) return set_error(hipErrorInvalidValue, "ionize: null particle array");
+		if (!(c.h[d] > 0.0) || !std::isfinite(c.h[d])) return set_error(hipErrorInvalidValue, "ionize: h must be > 0");
+		if (!std::isfinite(c.drift[d])) return set_error(hipErrorInvalidValue, "ionize: drift not finite");
+	}
+	if (!(c.nu >= 0.0) || !(c.sig >= 0.0) || !(c.wth >= 0.0) || !(c.vth >= 0.0) || !std::isfinite(c.nu) ||
+	    !std::isfinite(c.sig) || !std::isfinite(c.wth) || !std::isfinite(c.vth))
+		return set_error(hipErrorInvalidValue, "ionize: a rate, the threshold or vth is negative or not finite");
+	for (int q : {s, t})
+		if (pop.iStop[q] < pop.iStart[q] || pop.iStop[q] > pop.iStart[q + 1])
+			return set_error(hipErrorInvalidValue, "ionize: a species' live range is outside its slots");
+	const Span sp = species_span(pop, s);
+	if (workInts < pinc_hip_ionize_work(sp.n)) return set_error(hipErrorInvalidValue, "ionize: work too small");
+	if (sp.n <= 0) return 0;
+	const long nbl = chunk_blocks(sp.b0, sp.n, kIonChunk);
+	if (nbl >= (1L << 31)) return set_error(hipErrorInvalidValue, "ionize: too many particles");
+	const int nb = (int)nbl;
+	const IonSpan is = {sp.b0, sp.n, pop.iStop[s], pop.iStop[t], pop.iStart[s + 1] - pop.iStop[s],
+	                    pop.iStart[t + 1] - pop.iStop[t]};
+	int *counts = work, *offsets = work + nb;
+	hipStream_t st = (hipStream_t)stream;
+	const auto x = upto_nd(pop.x, pop.nd), v = upto_nd(pop.v, pop.nd);
+	// a cross section: every particle is an entry of the second stage; the
+	// rate alone: one draw lists the candidates (k_ionize)
+	const bool eager = c.sig != 0.0;
+	auto pass = [&](auto ND, auto WRITE) {
+		if (eager)
+			hipLaunchKernelGGL((k_ionize<ND, true, WRITE>), dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, v.a, v.b, v.c, is,
+			                   c, counts, offsets, nb, res);
+		else
+			hipLaunchKernelGGL((k_ionize<ND, false, WRITE>), dim3(nb), dim3(kThreads), 0, st, x.a, x.b, x.c, v.a, v.b, v.c,
+			                   is, c, counts, offsets, nb, res);
+	};
+	with_nd(pop.nd, [&](auto ND) { pass(ND, std::false_type{}); });
+	scan_ints(counts, nb, offsets, offsets + (nb + 1), st);
+	with_nd(pop.nd, [&](auto ND) { pass(ND, std::true_type{}); });
+	return check_launch("ionize");
 }
 
 extern "C" int pinc_hip_move_classify(pinc_pop_t pop, int s, int doMove, const double *thr,

@@ -5,8 +5,11 @@
  *   mccAlloc     the ini's [collisions] section, validated
  *   mccCollide   one pinc_hip_collide per species with a non-zero rate
  *   mccCounts    cumulative elastic / charge-exchange counts
+ *   mccIonize    one pinc_hip_ionize per species with an ionisation rate; the
+ *                species that grew are taken in as puMigrate takes immigrants
+ *   mccIonizations  cumulative births per projectile species
  *
- * The rule is pinc_hip_collide's (include/pinc_hip.h).
+ * The rules are pinc_hip_collide's and pinc_hip_ionize's (include/pinc_hip.h).
  */
 #define _GNU_SOURCE
 #include "pinc_internal.h"
@@ -18,6 +21,15 @@ struct Collisions {
 	pinc_collide_t par[PINC_MAX_SPECIES]; /* key set per launch */
 	unsigned long long seed, step;
 	unsigned long long *counts;           /* device: [s][2] */
+	/* ionisation: its own call counter, so that mccCollide's draws do not
+	 * depend on whether ionisation runs */
+	int ionActive[PINC_MAX_SPECIES];      /* an ionisation rate of the species is not zero */
+	pinc_ionize_t ion[PINC_MAX_SPECIES];  /* key set per launch */
+	unsigned long long ionStep;
+	unsigned long long births[PINC_MAX_SPECIES]; /* host: cumulative, per projectile */
+	unsigned long long *ionRes;           /* device: [s][2], births and the overflow word */
+	int *ionWork;                         /* device scratch of pinc_hip_ionize */
+	long ionWorkInts;
 };
 
 static const char *const kRateKeys[4] = {"collisions:elasticNu", "collisions:cexNu", "collisions:elasticSigma",
@@ -58,18 +70,42 @@ void pinc_mcc_mass_fraction(dictionary *ini) {
 Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo *mpiInfo) {
 	(void)mpiInfo;
 	const int ns = pop->nSpecies, nd = pop->nDims;
-	static const char *const known[9] = {"elasticNu", "cexNu", "elasticSigma", "cexSigma", "neutralMass", "neutralVth",
-	                                     "neutralDrift", "seed", "neutralMassFraction"};
+	static const char *const known[13] = {"elasticNu", "cexNu", "elasticSigma", "cexSigma", "neutralMass", "neutralVth",
+	                                      "neutralDrift", "seed", "neutralMassFraction", "ionNu", "ionSigma",
+	                                      "ionThreshold", "ionSpecies"};
 	int present = 0;
-	const char *unknown = pinc_ini_unknown_key(ini, "collisions", known, 9, &present);
+	const char *unknown = pinc_ini_unknown_key(ini, "collisions", known, 13, &present);
 	if (!present) return NULL;
 	if (unknown)
 		msg(ERROR, "%s is no key of [collisions] (elasticNu, cexNu, elasticSigma, cexSigma, neutralMass, neutralVth, "
-		           "neutralDrift, seed)", unknown);
+		           "neutralDrift, seed, ionNu, ionSigma, ionThreshold, ionSpecies)", unknown);
 	if (ns > PINC_MAX_SPECIES) msg(ERROR, "collisions: more than %d species", PINC_MAX_SPECIES);
 
 	double *rate[4];
 	for (int k = 0; k < 4; k++) rate[k] = rate_arr(ini, kRateKeys[k], ns);
+	/* ionisation: rates, the threshold speed (rate_arr's rules: one value per
+	 * species, >= 0, finite) and the species that receives the ions */
+	double *ionNu = rate_arr(ini, "collisions:ionNu", ns), *ionSig = rate_arr(ini, "collisions:ionSigma", ns);
+	double *ionWth = rate_arr(ini, "collisions:ionThreshold", ns);
+	int ionTarget[PINC_MAX_SPECIES] = {0}, anyIon = 0;
+	for (int s = 0; s < ns; s++) anyIon |= ionNu[s] > 0 || ionSig[s] > 0;
+	if (anyIon) {
+		if (!iniHas(ini, "collisions:ionSpecies"))
+			msg(ERROR, "collisions:ionSpecies (the species that receives the ions, one value per species) is required "
+			           "with an ionisation rate");
+		const int n = iniGetNElements(ini, "collisions:ionSpecies");
+		if (n != ns) msg(ERROR, "collisions:ionSpecies takes one value per species (%d), not %d", ns, n);
+		int *t = iniGetIntArr(ini, "collisions:ionSpecies", ns);
+		for (int s = 0; s < ns; s++) {
+			if (!(ionNu[s] > 0 || ionSig[s] > 0)) continue;
+			if (t[s] < 0 || t[s] >= ns)
+				msg(ERROR, "collisions:ionSpecies of species %d is %d: no species (0..%d)", s, t[s], ns - 1);
+			if (t[s] == s)
+				msg(ERROR, "collisions:ionSpecies of species %d is the projectile itself: the ions need another species", s);
+			ionTarget[s] = t[s];
+		}
+		free(t);
+	}
 	double vth = iniHas(ini, "collisions:neutralVth") ? iniGetDouble(ini, "collisions:neutralVth") : 0.0;
 	if (!(vth >= 0.0) || !isfinite(vth)) msg(ERROR, "collisions:neutralVth must be >= 0 and finite, not %g", vth);
 	double drift[3] = {0, 0, 0};
@@ -83,7 +119,7 @@ Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo
 		}
 		free(a);
 	}
-	int anyElastic = 0, any = 0;
+	int anyElastic = 0, any = anyIon;
 	for (int s = 0; s < ns; s++) {
 		anyElastic |= rate[0][s] > 0 || rate[2][s] > 0;
 		any |= rate[0][s] > 0 || rate[1][s] > 0 || rate[2][s] > 0 || rate[3][s] > 0;
@@ -125,6 +161,17 @@ Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo
 				p->h[d] = d < nd ? step[d] / step[0] : 1.0;
 			}
 			C->active[s] = p->nu[0] > 0 || p->nu[1] > 0 || p->sig[0] > 0 || p->sig[1] > 0;
+			pinc_ionize_t *q = &C->ion[s];
+			q->nu = ionNu[s];
+			q->sig = ionSig[s];
+			q->wth = ionWth[s];
+			q->vth = vth;
+			for (int d = 0; d < 3; d++) {
+				q->drift[d] = p->drift[d];
+				q->h[d] = p->h[d];
+			}
+			q->target = ionTarget[s];
+			C->ionActive[s] = q->nu > 0 || q->sig > 0;
 		}
 		free(step);
 		pinc_ctx_require();
@@ -132,8 +179,17 @@ Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo
 		           "collision counters");
 		pinc_check(pinc_hip_memset(C->counts, 0, 2 * PINC_MAX_SPECIES * sizeof(unsigned long long), g_pinc.stream),
 		           "collision counters");
+		if (anyIon) {
+			pinc_check(pinc_hip_malloc((void **)&C->ionRes, 2 * PINC_MAX_SPECIES * sizeof(unsigned long long)),
+			           "ionisation counters");
+			pinc_check(pinc_hip_memset(C->ionRes, 0, 2 * PINC_MAX_SPECIES * sizeof(unsigned long long), g_pinc.stream),
+			           "ionisation counters");
+		}
 	}
 	for (int k = 0; k < 4; k++) free(rate[k]);
+	free(ionNu);
+	free(ionSig);
+	free(ionWth);
 	return C;
 }
 
@@ -161,6 +217,71 @@ void mccCollide(Collisions *C, Population *pop) {
 	/* (pinc_pop_flush_host left the device arrays the truth: pSyncToHost reads them) */
 }
 
+/* species q grew by `births` at its tail: what puMigrate does after
+ * puMigrateImport (pinc_pusher.c).  The new slots' flags are not written, as
+ * an import leaves them; depEnd and cellValid stay, so that distr deposits the
+ * tail [depEnd, iStop) as it deposits immigrants */
+static void take_in_births(Population *pop, int q, long births) {
+	PincDevPop *dv = pop->dev;
+	const long before = pop->iStop[q] - pop->iStart[q];
+	pop->iStop[q] += births;
+	if (dv->sorted && dv->cntValid[q]) {
+		pinc_pop_t p = pinc_devpop(pop);
+		pinc_check(pinc_hip_count_keys(p, q, before, dv->geom, dv->tileWidth, dv->keyCnt[q], g_pinc.stream),
+		           "count the keys of the born");
+	}
+	dv->flagsValid = 0;
+}
+
+void mccIonize(Collisions *C, Population *pop) {
+	if (!C || !C->ionRes) return;
+	pinc_pop_flush_host(pop);
+	PincDevPop *dv = pop->dev;
+	if (dv->pending)
+		msg(ERROR, "mccIonize with a fused puAcc's move pending: ionise the settled particles, after puMigrate");
+	for (int s = 0; s < C->nSpecies; s++) {
+		if (!C->ionActive[s]) continue;
+		pinc_ionize_t par = C->ion[s];
+		const int t = par.target;
+		par.key = pinc_hip_ionize_key(C->seed, C->ionStep, g_pinc.rank, s);
+		pinc_pop_t p = pinc_devpop(pop);
+		const long need = pinc_hip_ionize_work(p.iStop[s] - p.iStart[s]);
+		if (need > C->ionWorkInts) {
+			pinc_check(pinc_hip_stream_sync(g_pinc.stream), "ionisation scratch");
+			pinc_hip_free(C->ionWork);
+			C->ionWorkInts = need + need / 4;
+			pinc_check(pinc_hip_malloc((void **)&C->ionWork, C->ionWorkInts * sizeof(int)), "ionisation scratch");
+		}
+		pinc_check(pinc_hip_ionize(p, s, par, C->ionWork, C->ionWorkInts, C->ionRes + 2 * s, g_pinc.stream), "ionize");
+		unsigned long long res[2];
+		pinc_check(pinc_hip_d2h(res, C->ionRes + 2 * s, sizeof(res), g_pinc.stream), "ionisation counters");
+		if (res[1]) {
+			const int q = pop->iStart[s + 1] - pop->iStop[s] <= pop->iStart[t + 1] - pop->iStop[t] ? s : t;
+			msg(ERROR, "ionisation: allocated only %li particles of specie %i", pop->iStart[q + 1] - pop->iStart[q], q);
+		}
+		const long births = (long)(res[0] - C->births[s]);
+		C->births[s] = res[0];
+		if (births) {
+			take_in_births(pop, s, births);
+			take_in_births(pop, t, births);
+		}
+		/* the electrons' new velocities are held to population:maxVel now, as
+		 * mccCollide's are (the born electrons are in the range by now) */
+		if (isfinite(g_pinc.maxVel)) {
+			pinc_check(pinc_hip_vel_assert(pinc_devpop(pop), s, g_pinc.maxVel, g_pinc.dErr, g_pinc.stream),
+			           "ionize: maxVel");
+			g_pinc.errSerial++;
+		}
+	}
+	C->ionStep++;
+}
+
+unsigned long long mccIonizations(const Collisions *C, int s) {
+	if (!C) return 0;
+	if (s < 0 || s >= C->nSpecies) msg(ERROR, "mccIonizations: species %d out of range", s);
+	return C->births[s];
+}
+
 void mccCounts(const Collisions *C, int s, unsigned long long out[2]) {
 	out[0] = out[1] = 0;
 	if (!C) return;
@@ -171,5 +292,7 @@ void mccCounts(const Collisions *C, int s, unsigned long long out[2]) {
 void mccFree(Collisions *C) {
 	if (!C) return;
 	pinc_hip_free(C->counts);
+	pinc_hip_free(C->ionRes);
+	pinc_hip_free(C->ionWork);
 	free(C);
 }

@@ -6,7 +6,8 @@
  * Loop order per step (main.c:197-274, single-add harness of SURVEY.md
  * Appendix A; literal=1 adds main.c:231-235's second FROMHALO add and the
  * extra solve):
- *   puMove [-> mccCollide] -> extractEmigrants -> puMigrate -> distr -> gHaloOp(add,rho,FROM)
+ *   puMove [-> mccCollide] -> extractEmigrants -> puMigrate [-> mccIonize] -> distr
+ *   -> gHaloOp(add,rho,FROM)
  *   -> solve -> gHaloOp(set,phi,TO) -> gFinDiff1st -> gHaloOp(set,E,TO)
  *   -> gMul(E,-1) -> acc (+KE) -> pSumKinEnergy -> gPotEnergy
  * The per-step asserts pVelAssertMax / pPosAssertInLocalFrame are folded into
@@ -224,9 +225,9 @@ static PincSim *sim_build(dictionary *ini, const PincSimOpts *opts) {
 	/* method selection (main.c:55-79) */
 	S->acc = (void (*)(Population *, Grid *))select(ini, "methods:acc", puAcc3D1_set, puAcc3D1KE_set, puAccND1_set,
 	                                                 puAccND1KE_set, puBoris3D1_set, puBoris3D1KE_set, puAccND2_set,
-	                                                 puAccND2KE_set);
+	                                                 puAccND2KE_set, puAccND0_set, puAccND0KE_set);
 	S->distr = (void (*)(const Population *, Grid *))select(ini, "methods:distr", puDistr3D1_set, puDistrND1_set,
-	                                                        puDistrND2_set);
+	                                                        puDistrND2_set, puDistrND0_set);
 	S->extractEmigrants = (void (*)(Population *, MpiInfo *))select(ini, "methods:migrate", puExtractEmigrants3D_set,
 	                                                                puExtractEmigrantsND_set);
 	void (*solverInterface)() = select(ini, "methods:poisson", mgSolver_set, sSolver_set);
@@ -277,6 +278,7 @@ static void sim_init(PincSim *S) {
 	}
 	S->extractEmigrants(pop, S->mpi);
 	puMigrate(pop, S->mpi, S->rho);
+	if (S->mcc) mccIonize(S->mcc, pop);
 	if (S->obj) {
 		/* capacitance matrix, then main.c:163-166: particles that start
 		 * inside the object are removed, their charge dropped */
@@ -316,6 +318,9 @@ static void sim_step(PincSim *S) {
 	if (S->mcc) mccCollide(S->mcc, pop);
 	S->extractEmigrants(pop, S->mpi);
 	puMigrate(pop, S->mpi, S->rho);
+	/* ionisation where every particle is inside the local frame: the pair is
+	 * born at its parent's position, and the deposit below carries it */
+	if (S->mcc) mccIonize(S->mcc, pop);
 	/* pPosAssertInLocalFrame (main.c:219) before anything deposits an
 	 * immigrant: a particle outside the local frame must not reach the
 	 * deposit's grid indexing */
@@ -523,6 +528,12 @@ int pinc_sim_op(PincSim *S, const char *op) {
 			return 1;
 		}
 		mccCollide(S->mcc, S->pop);
+	} else if (!strcmp(op, "ionize")) {
+		if (!S->mcc) {
+			msg(WARNING, "op ionize without [collisions] (or with every rate zero)");
+			return 1;
+		}
+		mccIonize(S->mcc, S->pop);
 	} else if (!strcmp(op, "step")) sim_step(S);
 	else {
 		msg(WARNING, "unknown op %s", op);
@@ -689,6 +700,16 @@ int pinc_sim_collisions(PincSim *S, int s, unsigned long long out[2]) {
 		return 1;
 	}
 	mccCounts(S->mcc, s, out);
+	return 0;
+}
+
+int pinc_sim_ionizations(PincSim *S, int s, unsigned long long *births) {
+	*births = 0;
+	if (s < 0 || s >= S->pop->nSpecies) {
+		msg(WARNING, "pinc_sim_ionizations: species %d out of range", s);
+		return 1;
+	}
+	*births = mccIonizations(S->mcc, s);
 	return 0;
 }
 

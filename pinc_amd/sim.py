@@ -221,6 +221,16 @@ class Sim:
             raise ValueError(f"collisions: no species {s}")
         return int(out[0]), int(out[1])
 
+    def ionizations(self, s: int) -> int:
+        """This rank's electron-ion pairs born by the impact of species s on
+        the neutral background since the simulation was created (the ini's
+        collisions:ionNu, ionSigma, ionThreshold, ionSpecies; zero without
+        them).  op("ionize") runs one ionisation step on its own."""
+        out = C.c_ulonglong()
+        if HOST.pinc_sim_ionizations(self._h, s, C.byref(out)):
+            raise ValueError(f"ionizations: no species {s}")
+        return int(out.value)
+
     @property
     def offset(self) -> np.ndarray:
         """This rank's offset of the local frame (particles()) to the global
