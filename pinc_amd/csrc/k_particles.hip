@@ -4147,6 +4147,10 @@ extern "C" int pinc_hip_init_species(pinc_pop_t pop, int s, pinc_geom_t g, long 
                                      double vth, unsigned long long seed, long *nOut,
                                      void *stream) {
 	hipStream_t st = (hipStream_t)stream;
+	if (nGlobal <= 0) {
+		*nOut = 0;
+		return 0;
+	}
 	LatticeArgs a;
 	a.nd = g.nd;
 	for (int d = 0; d < 3; d++) {
@@ -4385,6 +4389,7 @@ extern "C" int pinc_hip_scan_keys(const int *counts, long nKeys, int *offsets, i
 extern "C" int pinc_hip_rho_combine(double *rho, const double *const *acc, const double *charge, int ns, long n,
                                     void *stream) {
 	if (ns < 1 || ns > PINC_MAX_SPECIES) return set_error(hipErrorInvalidValue, "rho_combine: species");
+	if (n <= 0) return 0;
 	CombineArgs c;
 	c.ns = ns;
 	for (int s = 0; s < PINC_MAX_SPECIES; s++) {

@@ -1,6 +1,6 @@
 """Guarded device buffers shared by the GPU tests that call kernels through
-the C ABI: an array on the device between NaN guard elements, and bitwise
-comparison.
+the C ABI: an array on the device between NaN guard elements (integer guards
+for an integer array), and bitwise comparison.
 """
 import numpy as np
 
@@ -43,3 +43,34 @@ def same_bits(a, b):
 
 def nans(shape):
     return np.full(tuple(shape)[::-1], np.nan)
+
+
+class IntBuf:
+    """An integer array (any numpy integer type, bytes included) on the
+    device between `nguard` guard elements of its own type."""
+
+    def __init__(self, arr, guard=-77, nguard=16):
+        import torch
+        arr = np.ascontiguousarray(arr)
+        assert arr.dtype.kind in "iu" and arr.ndim == 1
+        self.n, self.lo = arr.size, nguard
+        self.host = np.full(self.n + 2 * nguard, guard, dtype=arr.dtype)
+        self.host[self.lo:self.lo + self.n] = arr
+        self.t = torch.from_numpy(self.host.copy()).cuda()
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr() + self.host.itemsize * self.lo
+
+    def get(self):
+        """the array now; the guards must hold their values"""
+        import torch
+        torch.cuda.synchronize()
+        a = self.t.cpu().numpy()
+        hi = self.lo + self.n
+        assert np.array_equal(a[:self.lo], self.host[:self.lo]) and np.array_equal(a[hi:], self.host[hi:]), \
+            "guard overwritten"
+        return a[self.lo:hi]
+
+    def unchanged(self):
+        return np.array_equal(self.get(), self.host[self.lo:self.lo + self.n])
