@@ -290,6 +290,11 @@ void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *m
  *                           required with an ionisation rate, read for the
  *                           species that have one, a valid index other than
  *                           the projectile's (else msg(ERROR))
+ *   coulombLog              nSpecies x nSpecies values, row-major: entry (a, b)
+ *                           is ln Lambda of binary Coulomb collisions between
+ *                           species a and b (pinc_hip_coulomb), 0 switches the
+ *                           pair off.  3-D only; the matrix must be symmetric,
+ *                           its entries >= 0 and finite (else msg(ERROR))
  * uAlloc takes the neutral's share of each pair mass, b = m_n / (m_s + m_n),
  * from the input's masses before it rewrites them and keeps it in the
  * dictionary as collisions:neutralMassFraction, which mccAlloc reads (on a
@@ -318,7 +323,25 @@ void puPhaseHist(Population *pop, int s, const PhaseSpec *spec, const MpiInfo *m
  * pinc_hip_ionize_key(seed, n, r, s) with a call counter n of its own, so
  * mccCollide's draws are the same with and without ionisation.  Nothing is
  * launched without an ionisation rate.  mccIonizations: the births caused by
- * projectile species s since mccAlloc on this rank. */
+ * projectile species s since mccAlloc on this rank.
+ * mccCoulomb runs one Coulomb collision step: one pinc_hip_coulomb per pair
+ * a <= b with a logarithm, in ascending (a, b), after puMigrate (every particle
+ * is then inside the local frame and every cell has one owner: no rank needs
+ * another's particles) and before mccIonize; msg(ERROR) while a fused puAcc's
+ * move is pending.  Its draws are those of pinc_hip_coulomb_key(seed, n, r, a,
+ * b) with a call counter n of its own, so neither mccCollide's nor mccIonize's
+ * draws change when it is switched on, and nothing is launched without a
+ * logarithm.  The coefficient of a pair is
+ *   K_ab = (q_a q_b / mu)^2 lnLambda / (8 pi W H),  mu = m_a m_b / (m_a + m_b),
+ * with the normalised charges and masses of the computational particles, W the
+ * real particles each stands for (uAlloc keeps its weights in the dictionary
+ * as collisions:macroWeight for this; msg(ERROR) in an input) and H the cell
+ * volume in stepSize[0]^3.  An unlike pair whose species differ in W is
+ * msg(ERROR): the rule assumes equal weights.  population:maxVel is applied to
+ * both species as in mccCollide.  mccCoulombCoef: K_ab (0 for a pair that is
+ * off); mccCoulombCounts: the pair's collisions since mccAlloc on this rank
+ * (waits for the stream); both take the pair in either order.
+ * mccCoulombActive: a pair has a logarithm. */
 typedef struct Collisions Collisions;
 Collisions *mccAlloc(const dictionary *ini, const Population *pop, const MpiInfo *mpiInfo);
 void mccCollide(Collisions *mcc, Population *pop);
@@ -326,6 +349,10 @@ void mccFree(Collisions *mcc);
 void mccCounts(const Collisions *mcc, int s, unsigned long long out[2]);
 void mccIonize(Collisions *mcc, Population *pop);
 unsigned long long mccIonizations(const Collisions *mcc, int s);
+void mccCoulomb(Collisions *mcc, Population *pop);
+int mccCoulombActive(const Collisions *mcc);
+double mccCoulombCoef(const Collisions *mcc, int a, int b);
+unsigned long long mccCoulombCounts(const Collisions *mcc, int a, int b);
 funPtr puExtractEmigrants3D_set(dictionary *ini);
 funPtr puExtractEmigrantsND_set(dictionary *ini);
 void puExtractEmigrants3D(Population *pop, MpiInfo *mpiInfo);
@@ -511,9 +538,17 @@ int pinc_sim_offset(PincSim *sim, int *offset);
  * (zeros without collisions; non-zero for a bad species).  Ionisation
  * (collisions:ionNu, ionSigma): every step, and the init sequence, ionises
  * right after puMigrate; pinc_sim_op(sim, "ionize") runs one ionisation step on
- * its own.  pinc_sim_ionizations: mccIonizations of species s into *births. */
+ * its own.  pinc_sim_ionizations: mccIonizations of species s into *births.
+ * Coulomb collisions (collisions:coulombLog): every step, and the init
+ * sequence, runs mccCoulomb between puMigrate and mccIonize;
+ * pinc_sim_op(sim, "coulomb") runs one step of them on its own (non-zero, and a
+ * warning, without an active pair).  pinc_sim_coulomb_count and
+ * pinc_sim_coulomb_coef: mccCoulombCounts and mccCoulombCoef of the pair
+ * (non-zero for a bad species). */
 int pinc_sim_collisions(PincSim *sim, int s, unsigned long long out[2]);
 int pinc_sim_ionizations(PincSim *sim, int s, unsigned long long *births);
+int pinc_sim_coulomb_count(PincSim *sim, int a, int b, unsigned long long *n);
+int pinc_sim_coulomb_coef(PincSim *sim, int a, int b, double *K);
 int pinc_sim_emigrants(PincSim *sim, long *nEmigrants);
 int pinc_sim_species(PincSim *sim, double *charge, double *mass);
 int pinc_sim_sync(PincSim *sim);

@@ -495,6 +495,94 @@ long pinc_hip_ionize_work(long n);
 long pinc_hip_ionize_chunk(void);
 /* the key of a launch (a pure host function: no device, no state) */
 unsigned long long pinc_hip_ionize_key(unsigned long long seed, unsigned long long step, int rank, int s);
+/* Binary Coulomb collisions between the particles of species a and b, a <= b
+ * (Takizuka & Abe 1977; an extension).  One launch treats one ordered pair of
+ * species; a == b is like-particle scattering.  The particles of a cell are
+ * paired with each other, and every pair scatters by an angle drawn for it.
+ * 3-D only (the scattering needs three velocity components).  The rule is
+ * fixed, so that it can be restated (tests/coulomb_ref.py):
+ *   parameters   K        the pair's coefficient K_ab;
+ *                         K == 0 switches the pair off: nothing is launched
+ *                fa, fb   the mass fractions mu / m_a and mu / m_b of the
+ *                         reduced mass mu (fa + fb = 1 for the host's values;
+ *                         1/2 each for a like pair)
+ *                h[d] = stepSize[d] / stepSize[0]
+ *   Units as at pinc_hip_collide: the physics is done on w_d = h_d v_d, results
+ *   go back as v_d = w_d / h_d; fp64 throughout, products and sums are not
+ *   fused, cos and sin of pi t are cospi(t) and sinpi(t).
+ *   cell         with T_d the rank's true cells (g.T[d], g.nloc for d = 2),
+ *                c_d = min(max((int)x_d, 1), T_d) - 1 and
+ *                cell = c_0 + T_0 (c_1 + T_1 c_2): the integer cell of the
+ *                position in the local frame, clamped to the true cells.  It
+ *                differs from the cell pinc_hip_count_keys counts in two
+ *                ways: that one is the cell of x + v (where the next push
+ *                takes the particle) and is clamped to the ghost layer 0..T+1.
+ *                Positions are read, never written.
+ *   keys         key = pinc_hip_coulomb_key(seed, step, rank, a, b)
+ *                    = mix64(pinc_hip_collide_key(seed, step, rank, a)
+ *                            ^ 0x636F756C6F6D62 ^ mix64(a PINC_MAX_SPECIES + b))
+ *                key_s    = mix64(key ^ 1) for species a, mix64(key ^ 2) for b
+ *                key_pair = mix64(key ^ 3) where the first-named particle of a
+ *                           collision is of species a, mix64(key ^ 4) where it
+ *                           is of species b (a != b)
+ *                (mix64, uni: the counter RNG of pinc_hip_collide.)
+ *   order        the members of species s in a cell, sorted ascending by
+ *                (mix64(key_s ^ mix64(j)), j), j the species-local index
+ *                i - iStart[s]: a total order that does not depend on how the
+ *                members were gathered.
+ *   like pairs (a == b), the cell's list L of length N:
+ *                N < 2: nothing.  N even: the pairs (L[2m], L[2m+1]).  N odd:
+ *                the triple (L0, L1), (L1, L2), (L2, L0), applied in that
+ *                order, each with f = 1/2 and on the velocities the one before
+ *                left; then (L[3+2m], L[4+2m]).
+ *   unlike pairs (a < b): A is the longer list and B the shorter, A that of
+ *                species a on equal lengths.  With Q = |A| / |B| (integer) and
+ *                R = |A| mod |B|, B[k] collides in turn with Q + 1 consecutive
+ *                members of A for k < R and with Q otherwise, walking A in
+ *                order from A[0]; it carries its velocity from one partner to
+ *                the next.  An empty B: nothing.
+ *   one collision of p (first-named: L[2m]; L0, L1, L2 for the triple's three
+ *   pairs; the A-member) with q, f = 1 outside a triple:
+ *     1. g_d = w_p,d - w_q,d; gp = sqrt(gx gx + gy gy),
+ *        g = sqrt((gx gx + gy gy) + gz gz).  No collision if g == 0.
+ *     2. var = ((K nLow) f) / ((g g) g), nLow the shorter of the two lists'
+ *        lengths in this cell (N for a like pair)
+ *     3. u_k = uni(key_pair, 4 j + k), j the species-local index of p: every
+ *        collision of a launch has a counter block of its own (u3 is not used)
+ *     4. var < 1:  dl = (sqrt(var) sqrt(-2 ln u0)) cospi(2 u1),
+ *                  sinT = 2 dl / (1 + dl dl), omc = 2 dl dl / (1 + dl dl)
+ *        else:     c = 1 - 2 u0, sinT = sqrt((1 - c)(1 + c)), omc = 1 - c
+ *        (omc = 1 - cos Theta), cphi = cospi(2 u2), sphi = sinpi(2 u2)
+ *     5. gp > 0:   Dx = (gx/gp) gz sinT cphi - (gy/gp) g sinT sphi - gx omc
+ *                  Dy = (gy/gp) gz sinT cphi + (gx/gp) g sinT sphi - gy omc
+ *                  Dz = -gp sinT cphi - gz omc
+ *        gp == 0:  D = (gz sinT cphi, gz sinT sphi, -gz omc)   (g = |gz|; the
+ *                  sign of gz is kept, so that |g + D| = g in both directions)
+ *     6. w_p += (mu / m_p) D, w_q -= (mu / m_q) D
+ * counts[0] += the collisions applied in this launch (device memory,
+ * accumulated, not cleared); a pair with g == 0 is not counted and not
+ * written.  Only velocities of particles that collided are written.  work:
+ * pinc_hip_coulomb_work(nA, nB, nCells) ints of device scratch for the live
+ * particles of the two species (nB = 0 for a == b) and the rank's true cells.
+ * Errors (nothing is launched): a or b outside the population's species, or
+ * a > b; nd != 3 (population or geometry); a null array, scratch or counter;
+ * work too small; a negative or non-finite K; a mass fraction outside (0, 1);
+ * h_d <= 0. */
+typedef struct {
+	double K;
+	double fa, fb;    /* mu / m_a, mu / m_b */
+	double h[3];      /* as pinc_collide_t */
+	unsigned long long key;
+} pinc_coulomb_t;
+int pinc_hip_coulomb(pinc_pop_t pop, int a, int b, pinc_geom_t geom, pinc_coulomb_t params, int *work, long workInts,
+                     unsigned long long *counts, void *stream);
+/* ints of scratch */
+long pinc_hip_coulomb_work(long nA, long nB, long nCells);
+/* the longest cell list a wave orders in LDS (a build constant; tests): a
+ * longer one is ordered from global memory, with the same result */
+long pinc_hip_coulomb_cell_cap(void);
+/* the key of a launch (a pure host function: no device, no state) */
+unsigned long long pinc_hip_coulomb_key(unsigned long long seed, unsigned long long step, int rank, int a, int b);
 /* pVelAssertMax (population.c:342-365) over species s: a velocity component
  * above maxVel sets bit 0 of *errFlag */
 int pinc_hip_vel_assert(pinc_pop_t pop, int s, double maxVel, int *errFlag, void *stream);

@@ -120,6 +120,8 @@ _sigs = {
     "pinc_sim_offset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "pinc_sim_collisions": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "pinc_sim_ionizations": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "pinc_sim_coulomb_count": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "pinc_sim_coulomb_coef": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "pinc_sim_emigrants": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pinc_sim_species": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pinc_sim_sync": (C.c_int, [C.c_void_p]),

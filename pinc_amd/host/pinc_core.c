@@ -450,6 +450,7 @@ Units *uAlloc(dictionary *ini) {
 	} else {
 		msg(ERROR, "methods:normalization not valid (must be SI or semiSI)");
 	}
+	pinc_mcc_macro_weight(ini, u->weights, u->nSpecies); /* (uNormalize folds them into charge and mass) */
 	double X = u->length, T = u->time, Q = u->charge, M = u->mass, D = u->nDims;
 	u->hyperArea = pow(X, D - 1);
 	u->hyperVolume = pow(X, D);

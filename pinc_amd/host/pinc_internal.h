@@ -367,6 +367,9 @@ void pinc_literal_second_fold(const Population *pop, Grid *rho, int order);
 /* collisions:neutralMass's share of each pair mass, taken from the input's
  * masses before uAlloc rewrites them (pinc_mcc.c) */
 void pinc_mcc_mass_fraction(dictionary *ini);
+/* uAlloc leaves the real particles per computational particle in the ini for
+ * mccAlloc's Coulomb coefficients (only with collisions:coulombLog) */
+void pinc_mcc_macro_weight(dictionary *ini, const double *weights, int ns);
 /* the first key of [section] that is none of known[0..n) (names without the
  * section), or NULL; *count, if set: the keys the section has (pinc_core.c) */
 const char *pinc_ini_unknown_key(const dictionary *ini, const char *section, const char *const *known, int n, int *count);

@@ -6,7 +6,8 @@
  * Loop order per step (main.c:197-274, single-add harness of SURVEY.md
  * Appendix A; literal=1 adds main.c:231-235's second FROMHALO add and the
  * extra solve):
- *   puMove [-> mccCollide] -> extractEmigrants -> puMigrate [-> mccIonize] -> distr
+ *   puMove [-> mccCollide] -> extractEmigrants -> puMigrate [-> mccCoulomb] [-> mccIonize]
+ *   -> distr
  *   -> gHaloOp(add,rho,FROM)
  *   -> solve -> gHaloOp(set,phi,TO) -> gFinDiff1st -> gHaloOp(set,E,TO)
  *   -> gMul(E,-1) -> acc (+KE) -> pSumKinEnergy -> gPotEnergy
@@ -278,6 +279,7 @@ static void sim_init(PincSim *S) {
 	}
 	S->extractEmigrants(pop, S->mpi);
 	puMigrate(pop, S->mpi, S->rho);
+	if (S->mcc) mccCoulomb(S->mcc, pop);
 	if (S->mcc) mccIonize(S->mcc, pop);
 	if (S->obj) {
 		/* capacitance matrix, then main.c:163-166: particles that start
@@ -318,6 +320,10 @@ static void sim_step(PincSim *S) {
 	if (S->mcc) mccCollide(S->mcc, pop);
 	S->extractEmigrants(pop, S->mpi);
 	puMigrate(pop, S->mpi, S->rho);
+	/* Coulomb collisions pair the particles of a cell: after the migration
+	 * every particle is inside the local frame and every cell has one owner,
+	 * so no rank needs another's particles */
+	if (S->mcc) mccCoulomb(S->mcc, pop);
 	/* ionisation where every particle is inside the local frame: the pair is
 	 * born at its parent's position, and the deposit below carries it */
 	if (S->mcc) mccIonize(S->mcc, pop);
@@ -528,6 +534,12 @@ int pinc_sim_op(PincSim *S, const char *op) {
 			return 1;
 		}
 		mccCollide(S->mcc, S->pop);
+	} else if (!strcmp(op, "coulomb")) {
+		if (!mccCoulombActive(S->mcc)) {
+			msg(WARNING, "op coulomb without collisions:coulombLog (or with every entry zero)");
+			return 1;
+		}
+		mccCoulomb(S->mcc, S->pop);
 	} else if (!strcmp(op, "ionize")) {
 		if (!S->mcc) {
 			msg(WARNING, "op ionize without [collisions] (or with every rate zero)");
@@ -710,6 +722,27 @@ int pinc_sim_ionizations(PincSim *S, int s, unsigned long long *births) {
 		return 1;
 	}
 	*births = mccIonizations(S->mcc, s);
+	return 0;
+}
+
+static int coulomb_pair_ok(const PincSim *S, const char *who, int a, int b) {
+	const int ns = S->pop->nSpecies;
+	if (a >= 0 && a < ns && b >= 0 && b < ns) return 1;
+	msg(WARNING, "%s: pair %d, %d out of range", who, a, b);
+	return 0;
+}
+
+int pinc_sim_coulomb_count(PincSim *S, int a, int b, unsigned long long *n) {
+	*n = 0;
+	if (!coulomb_pair_ok(S, "pinc_sim_coulomb_count", a, b)) return 1;
+	*n = mccCoulombCounts(S->mcc, a, b);
+	return 0;
+}
+
+int pinc_sim_coulomb_coef(PincSim *S, int a, int b, double *K) {
+	*K = 0.0;
+	if (!coulomb_pair_ok(S, "pinc_sim_coulomb_coef", a, b)) return 1;
+	*K = mccCoulombCoef(S->mcc, a, b);
 	return 0;
 }
 

@@ -231,6 +231,23 @@ class Sim:
             raise ValueError(f"ionizations: no species {s}")
         return int(out.value)
 
+    def coulomb_count(self, a: int, b: int) -> int:
+        """This rank's binary Coulomb collisions between species a and b since
+        the simulation was created (the ini's collisions:coulombLog; zero
+        without it).  op("coulomb") runs one step of them on its own."""
+        out = C.c_ulonglong()
+        if HOST.pinc_sim_coulomb_count(self._h, a, b, C.byref(out)):
+            raise ValueError(f"coulomb_count: no species pair {a}, {b}")
+        return int(out.value)
+
+    def coulomb_coef(self, a: int, b: int) -> float:
+        """K_ab of pinc_hip_coulomb for species a and b in the code's units
+        (0 for a pair without a Coulomb logarithm)."""
+        out = C.c_double()
+        if HOST.pinc_sim_coulomb_coef(self._h, a, b, C.byref(out)):
+            raise ValueError(f"coulomb_coef: no species pair {a}, {b}")
+        return float(out.value)
+
     @property
     def offset(self) -> np.ndarray:
         """This rank's offset of the local frame (particles()) to the global
