@@ -140,6 +140,10 @@ struct PincDevPop {
 	                                       (materialised before its E was written, pinc_grid_touch) */
 	Grid *pendingE;                     /* E of the pending push's kick (pinc_pending_vel) */
 	unsigned long long pendingESerial, pendingEGen; /* ... its serial and write count then */
+	/* this population's last push round that kicked (push_all with an E):
+	 * process-unique and never 0, so it names the population and the round
+	 * even where pFree and pAlloc reuse an address (PincDevGrid.scaledAllSerial) */
+	unsigned long long pushSerial;
 	/* adaptive sort schedule (population:sortFraction > 0): a species is
 	 * sorted once the fraction of its particles that left their cell since
 	 * its last sort would pass sortFraction, at most sortMax pushes apart */
@@ -171,6 +175,9 @@ struct PincDevPop {
 	 * pVelMaxwell) and is the truth until the next device operator uploads
 	 * it (pinc_pop_flush_host): main.c never calls pSyncToDevice */
 	int hostDirty;
+	/* lattice index of each host particle (pPosLattice; pVelMaxwell's draws
+	 * are keyed by it), one table per population */
+	long *hostIds;
 	/* multi-rank migration buffers (AoS records: nd pos, nd vel, ne) */
 	double *sendBuf[2], *recvBuf[2];
 	long sendCap, recvCap;
@@ -195,6 +202,10 @@ struct PincDevGrid {
 	double *scaled;     /* E as rescaled for the species being pushed (lazy) */
 	double *scaledAll;  /* every species' rescaled E, one pass per push round (lazy) */
 	int scaledAllS;     /* species it holds room for */
+	/* the push round that filled scaledAll (PincDevPop.pushSerial of the
+	 * population that pushed; 0: none).  Populations may share one E, and each
+	 * round refills the buffer with the pushing population's q/m chain. */
+	unsigned long long scaledAllSerial;
 	/* sharded multigrid (phi only): this rank's slab with extOff halo planes
 	 * on each side, extPlanes planes in all, owned by the solver */
 	double *ext;

@@ -14,8 +14,6 @@
 #include "pinc_internal.h"
 #include <math.h>
 
-static long *g_hostIds = NULL; /* lattice index of each host particle */
-
 static void ws_alloc(pinc_extract_ws_t *ws, long cap) {
 	memset(ws, 0, sizeof(*ws));
 	ws->cap = cap;
@@ -253,6 +251,7 @@ void pFree(Population *p) {
 			pinc_hip_free(dv->recvBuf[k]);
 		}
 		pinc_hip_free(dv->phaseHist);
+		free(dv->hostIds);
 		free(dv);
 	}
 	free(p->pos);
@@ -264,8 +263,6 @@ void pFree(Population *p) {
 	free(p->kinEnergy);
 	free(p->potEnergy);
 	free(p);
-	free(g_hostIds);
-	g_hostIds = NULL;
 }
 
 pinc_pop_t pinc_devpop(const Population *pop) {
@@ -279,7 +276,7 @@ static void host_arrays(Population *p) {
 	long n = (long)p->nDims * p->iStart[p->nSpecies];
 	if (!p->pos) p->pos = calloc(n ? n : 1, sizeof(double));
 	if (!p->vel) p->vel = calloc(n ? n : 1, sizeof(double));
-	if (!g_hostIds) g_hostIds = calloc(p->iStart[p->nSpecies] + 1, sizeof(long));
+	if (!p->dev->hostIds) p->dev->hostIds = calloc(p->iStart[p->nSpecies] + 1, sizeof(long));
 }
 
 void pToLocalFrame(Population *p, const MpiInfo *m) {
@@ -333,7 +330,7 @@ void pPosLattice(const dictionary *ini, Population *p, const MpiInfo *m) {
 				if (k >= p->iStart[s + 1])
 					msg(ERROR, "allocated only %li particles of specie %i per node", p->iStart[s + 1] - p->iStart[s], s);
 				for (int d = 0; d < nd; d++) p->pos[k * nd + d] = x[d];
-				g_hostIds[k] = i;
+				p->dev->hostIds[k] = i;
 				k++;
 			}
 		}
@@ -395,7 +392,7 @@ void pVelMaxwell(const dictionary *ini, Population *p, unsigned long long seed) 
 	double *vth = iniGetDoubleArr(ini, "population:thermalVelocity", ns);
 	for (int s = 0; s < ns; s++)
 		for (long i = p->iStart[s]; i < p->iStop[s]; i++) {
-			unsigned long long c = (((unsigned long long)s << 40) | (unsigned long long)g_hostIds[i]) * 3ULL;
+			unsigned long long c = (((unsigned long long)s << 40) | (unsigned long long)p->dev->hostIds[i]) * 3ULL;
 			for (int d = 0; d < nd; d++) p->vel[i * nd + d] = drift[s] + vth[s] * gauss(seed, c + d);
 		}
 	free(drift);

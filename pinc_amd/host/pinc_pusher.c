@@ -412,6 +412,8 @@ static void push_phase_report(const unsigned long long *dts, const unsigned long
  * its output in cell order instead (to altX/altV, counting sort on the cell
  * counts of its input), and the push before it counts those cells.  Returns
  * 1 if this push sorted. */
+static unsigned long long g_pushSerial; /* push rounds that kicked, over all populations */
+
 static int push_all(Population *pop, Grid *E, double *const *xout) {
 	PincDevPop *dv = pop->dev;
 	pinc_geom_t g = dv->geom;
@@ -477,10 +479,15 @@ static int push_all(Population *pop, Grid *E, double *const *xout) {
 				           "E scaled");
 				eg->scaledAllS = pop->nSpecies;
 			}
-			if (s == 0)
+			if (s == 0) {
 				pinc_check(pinc_hip_field_chain_all(eg->d, eg->scaledAll, eg->n, dv->qm, dv->mq, 1.0, pop->nSpecies,
 				                                    g_pinc.stream),
 				           "E chain");
+				/* the buffer now holds this population's chain of this round
+				 * (pinc_pending_vel reuses it only then) */
+				dv->pushSerial = ++g_pushSerial;
+				eg->scaledAllSerial = dv->pushSerial;
+			}
 			a.Es = eg->scaledAll + (long)s * eg->n;
 			a.kick = 1;
 		}
@@ -669,8 +676,12 @@ void pinc_pending_vel(const Population *pop, int s, double *const *dst) {
 		           "sorting push");
 	PincDevGrid *eg = dv->pendingE->dev;
 	/* species s's rescaled E of the push round (E unchanged since: checked
-	 * above), else made here */
-	const double *es = eg->scaledAll && s < eg->scaledAllS ? eg->scaledAll + (long)s * eg->n : NULL;
+	 * above), while the buffer is still this population's chain of that round:
+	 * another population that kicked with the same E since has refilled it
+	 * with its own q/m (and, with more species, reallocated it).  Else made
+	 * here from this population's q/m. */
+	const int mine = eg->scaledAll && eg->scaledAllSerial == dv->pushSerial && dv->pushSerial != 0;
+	const double *es = mine && s < eg->scaledAllS ? eg->scaledAll + (long)s * eg->n : NULL;
 	if (!es) {
 		if (!eg->scaled) pinc_check(pinc_hip_malloc((void **)&eg->scaled, eg->n * sizeof(double)), "E scaled");
 		pinc_check(pinc_hip_field_chain(eg->d, eg->scaled, eg->n, dv->qm, dv->mq, 1.0, s, g_pinc.stream), "E chain");

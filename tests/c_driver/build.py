@@ -1,7 +1,7 @@
 """Compile the C callers under tests/c_driver/ (pinc_main.c: regular()
 through select(); pinc_objmain.c: main.c's object loop through the
 reference's object API; pinc_mainc.c: main.c's main() and regular() call for
-call) against the in-tree libpinc.so (test
+call; pinc_twopop.c: two populations that share one E) against the in-tree libpinc.so (test
 infrastructure; called by __graft_entry__.build() and the tests)."""
 from __future__ import annotations
 
@@ -30,3 +30,4 @@ if __name__ == "__main__":
     print(build())
     print(build("pinc_objmain"))
     print(build("pinc_mainc"))
+    print(build("pinc_twopop"))
